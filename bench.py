@@ -10,6 +10,10 @@ timed region.  A "step" is one `AnnealedImportanceSampler.sample_and_log_weights
 (+ the RCCL all-gather of the particles when --gpus > 1).
 
 Prints ONE JSON line (rank 0): value = chains produced by all ranks / max-over-ranks time.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the line used to carry
+(eval-mode and fast-mode rows, rooflines, trained-flow ESS, spline cfg 3, trainer iteration, CPU baseline).
+--dump-outputs DIR writes what the last timed step returned (x, log_w, log_q; float32 .npy) for output-for-output comparisons.
 """
 import argparse
 import json
@@ -243,6 +247,15 @@ def trainer_iteration(dev):
     return out
 
 
+def dump_outputs(out_dir, x, log_w, log_q):
+    """The arrays the timed step returned in its last step, as DIR/<name>.npy in float32 (1024 x 32 + 2 x 1024 floats at the
+    headline size, far below the 64 MB cap; every run with the same arguments draws the same inputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("x", x), ("log_w", log_w), ("log_q", log_q)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _relaunch_under_torchrun(args):
     """`python bench.py --gpus N` started directly (no torchrun environment): start N ranks of this same script, one per
     GPU, under torch.distributed.run on 127.0.0.1 and hand its exit code back.  (The driver's own torchrun command line
@@ -281,7 +294,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary rows (eval / fast mode, rooflines, spline cfg 3, trainer, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="headline")
     ap.add_argument("--chains-per-gpu", type=int, default=None)
     ap.add_argument("--layers", type=int, default=None)
@@ -359,6 +376,8 @@ def main():
             out = step()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, *out)
         if rank == 0:
             print(json.dumps({"metric": "AIS samples/sec (+ESS), ManyWell-32, 8 intermediate dists",
                               "value": world * B_PER_GPU * args.steps / elapsed, "unit": "AIS samples/s", "n_gpus": world,
@@ -408,11 +427,95 @@ def main():
         out = step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *out)
     info = ais.get_logging_info()                   # (N > 1: this rank's chains; `ess_gathered` below is the whole set)
     if distributed:
         info["log_Z"] = float(sharded.logging_info["log_Z"])
     ess_all = float(fa.effective_sample_size(out[1]).item())
     slab_gathers = sharded.n_slab_gathers if distributed else 0
+    if args.full:
+        extra = full_rows(args, ais, hmc, step, out, sharded, dev, rank, world, custom, barrier, max_over_ranks)
+    else:
+        extra = None
+
+    bad = []
+    if rank == 0:
+        total = world * B_PER_GPU * args.steps
+        line = {
+            "metric": "AIS samples/sec (+ESS), ManyWell-32, %d intermediate dists" % M,
+            "value": total / elapsed, "unit": "AIS samples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s%s: ManyWell-32 AIS, RealNVP %dx(16-320-320-32)+InvAffine (seeded default init, last coupling "
+                                   "Linears N(0, 0.01^2)), HMC L=5 n_outer=1, M=%d linear beta, alpha=2 (target p^2/q), "
+                                   "step-size tuning on" % (args.workload, " (modified)" if custom else "", K_LAYERS, M),
+                       "chains_per_gpu": B_PER_GPU, "global_chains": world * B_PER_GPU,
+                       "parallelism": (f"chains sharded x{world}: single-device step-size rule ({slab_gathers} acceptance-slab "
+                                       "all-gathers per step) + one particle all-gather" if world > 1 else "single GPU")},
+            "ranks": world, "backend": ("rccl" if backend == "nccl" else backend) if distributed else None,
+            "rccl_ranks": (dist.get_world_size() if (distributed and backend == "nccl") else 0),
+            "process_group_ranks": (dist.get_world_size() if distributed else 1),
+            "collectives_per_step": (slab_gathers + 1) if distributed else 0,
+            "lib_srchash": _lib_srchash(),
+            "gathered_rows": int(out[0].shape[0]),
+            "slab_all_gathers_per_step": slab_gathers,
+            "ess_ais": info["ess_ais"], "ess_gathered": ess_all, "log_Z": info["log_Z"],
+            "p_accept_first": info.get("dist0_p_accept_0"),
+        }
+        if extra is not None:
+            line["collectives_per_step_eval_mode"] = (extra["slab_gathers_eval"] + 1) if distributed else 0
+            line["particle_all_gather_us"] = extra["gather_us"]
+            line["value_eval_mode"] = total / extra["elapsed_eval"]
+            line["roofline"] = extra["roof"]
+            line["roofline_resample"] = extra["roof_extra"]
+            line["ess_trained"] = extra["ess_trained"]
+            line["spline_cfg3"] = extra["spline3"]
+            line["trainer_iteration"] = extra["trainer_row"]
+            ess_trained_fast, info_fast, elapsed_fast = extra["ess_trained_fast"], extra["info_fast"], extra["elapsed_fast"]
+            line["fast_mode"] = {
+                "what": "NOT the parity path: the two 320x320 GEMMs of every coupling layer with bf16 operands (weights rounded at pack "
+                        "time, activations as they are fetched; fp32 accumulation) inside the chain-initialisation and transition "
+                        "kernels - up to 1152 chains on the 4-chain tiles with fused stages (v_mfma_f32_4x4x4_16b_bf16, half the "
+                        "weight stream), above on the 16-chain tiles (v_mfma_f32_16x16x32_bf16); log q deviates 1e-3 .. 1e-2 from "
+                        "the fp32 kernels",
+                "value": total / elapsed_fast, "unit": "AIS samples/s", "ms_per_step": elapsed_fast / args.steps * 1e3,
+                "speedup_vs_value": elapsed / elapsed_fast, "ess_ais": info_fast["ess_ais"], "log_Z": info_fast["log_Z"],
+                "ess_trained": None if ess_trained_fast is None else
+                {t: {k: ess_trained_fast[t][k] for k in ("ess_ais_hip", "ess_ais_reference", "rel_diff", "log_Z_hip")}
+                 for t in ("target_p", "target_g")},
+            }
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(flow_state)
+                line["speedup_vs_cpu"] = line["value"] / line["cpu_baseline"]["value"]
+        # N > 1: what the line claims about the collectives is checked, not assumed (a run that silently fell back to another
+        # backend, another loop form or rank-local step sizes fails here instead of producing a plausible number)
+        if distributed:
+            if backend == "nccl" and line["rccl_ranks"] != world:
+                bad.append(f"rccl_ranks {line['rccl_ranks']} != world {world}")
+            if line["process_group_ranks"] != world:
+                bad.append(f"process group holds {line['process_group_ranks']} ranks, launched {world}")
+            if line["collectives_per_step"] != M + 1:
+                bad.append(f"tuned step issued {line['collectives_per_step']} collectives, expected M + 1 = {M + 1}")
+            if extra is not None and line["collectives_per_step_eval_mode"] != 1:
+                bad.append(f"eval-mode step issued {line['collectives_per_step_eval_mode']} collectives, expected 1")
+            if line["gathered_rows"] != world * B_PER_GPU:
+                bad.append(f"gathered {line['gathered_rows']} rows, expected {world * B_PER_GPU}")
+        line["multi_gpu_checks"] = "ok" if not bad else bad
+        print(json.dumps(line), flush=True)
+    if distributed:
+        dist.barrier()                      # rank 0 measured the roofline leg alone; leave together
+        dist.destroy_process_group()
+    if rank == 0 and bad:
+        raise SystemExit("bench.py: multi-GPU consistency checks failed: " + "; ".join(bad))
+
+
+def full_rows(args, ais, hmc, step, out, sharded, dev, rank, world, custom, barrier, max_over_ranks):
+    """--full: the rows next to the headline, measured after its timed steps (eval mode, particle all-gather, fast mode,
+    rooflines, trained-flow ESS, spline cfg 3, trainer iteration; the CPU baseline is added by the caller)."""
+    import fab_torch_amd as fa
+    from fab_torch_amd import parallel
+    distributed = world > 1
     # second row of SURVEY.md section 8d: the same K steps with step-size tuning frozen (evaluation mode)
     hmc.set_eval_mode(True)
     barrier()
@@ -531,72 +634,10 @@ def main():
     spline3 = spline_cfg3(dev) if (rank == 0 and world == 1 and not custom and args.workload == "headline") else None
     trainer_row = trainer_iteration(dev) if (rank == 0 and world == 1 and not custom and args.workload == "headline") else None
 
-    bad = []
-    if rank == 0:
-        total = world * B_PER_GPU * args.steps
-        line = {
-            "metric": "AIS samples/sec (+ESS), ManyWell-32, %d intermediate dists" % M,
-            "value": total / elapsed, "unit": "AIS samples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s%s: ManyWell-32 AIS, RealNVP %dx(16-320-320-32)+InvAffine (seeded default init, last coupling "
-                                   "Linears N(0, 0.01^2)), HMC L=5 n_outer=1, M=%d linear beta, alpha=2 (target p^2/q), "
-                                   "step-size tuning on" % (args.workload, " (modified)" if custom else "", K_LAYERS, M),
-                       "chains_per_gpu": B_PER_GPU, "global_chains": world * B_PER_GPU,
-                       "parallelism": (f"chains sharded x{world}: single-device step-size rule ({slab_gathers} acceptance-slab "
-                                       "all-gathers per step) + one particle all-gather" if world > 1 else "single GPU")},
-            "ranks": world, "backend": ("rccl" if backend == "nccl" else backend) if distributed else None,
-            "rccl_ranks": (dist.get_world_size() if (distributed and backend == "nccl") else 0),
-            "process_group_ranks": (dist.get_world_size() if distributed else 1),
-            "collectives_per_step": (slab_gathers + 1) if distributed else 0,
-            "collectives_per_step_eval_mode": (slab_gathers_eval + 1) if distributed else 0,
-            "lib_srchash": _lib_srchash(),
-            "gathered_rows": int(out[0].shape[0]), "particle_all_gather_us": gather_us,
-            "slab_all_gathers_per_step": slab_gathers,
-            "value_eval_mode": total / elapsed_eval,
-            "ess_ais": info["ess_ais"], "ess_gathered": ess_all, "log_Z": info["log_Z"],
-            "p_accept_first": info.get("dist0_p_accept_0"),
-            "roofline": roof,
-            "roofline_resample": roof_extra,
-            "ess_trained": ess_trained,
-            "spline_cfg3": spline3,
-            "trainer_iteration": trainer_row,
-            "fast_mode": {
-                "what": "NOT the parity path: the two 320x320 GEMMs of every coupling layer with bf16 operands (weights rounded at pack "
-                        "time, activations as they are fetched; fp32 accumulation) inside the chain-initialisation and transition "
-                        "kernels - up to 1152 chains on the 4-chain tiles with fused stages (v_mfma_f32_4x4x4_16b_bf16, half the "
-                        "weight stream), above on the 16-chain tiles (v_mfma_f32_16x16x32_bf16); log q deviates 1e-3 .. 1e-2 from "
-                        "the fp32 kernels",
-                "value": total / elapsed_fast, "unit": "AIS samples/s", "ms_per_step": elapsed_fast / args.steps * 1e3,
-                "speedup_vs_value": elapsed / elapsed_fast, "ess_ais": info_fast["ess_ais"], "log_Z": info_fast["log_Z"],
-                "ess_trained": None if ess_trained_fast is None else
-                {t: {k: ess_trained_fast[t][k] for k in ("ess_ais_hip", "ess_ais_reference", "rel_diff", "log_Z_hip")}
-                 for t in ("target_p", "target_g")},
-            },
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(flow_state)
-            line["speedup_vs_cpu"] = line["value"] / line["cpu_baseline"]["value"]
-        # N > 1: what the line claims about the collectives is checked, not assumed (a run that silently fell back to another
-        # backend, another loop form or rank-local step sizes fails here instead of producing a plausible number)
-        if distributed:
-            if backend == "nccl" and line["rccl_ranks"] != world:
-                bad.append(f"rccl_ranks {line['rccl_ranks']} != world {world}")
-            if line["process_group_ranks"] != world:
-                bad.append(f"process group holds {line['process_group_ranks']} ranks, launched {world}")
-            if line["collectives_per_step"] != M + 1:
-                bad.append(f"tuned step issued {line['collectives_per_step']} collectives, expected M + 1 = {M + 1}")
-            if line["collectives_per_step_eval_mode"] != 1:
-                bad.append(f"eval-mode step issued {line['collectives_per_step_eval_mode']} collectives, expected 1")
-            if line["gathered_rows"] != world * B_PER_GPU:
-                bad.append(f"gathered {line['gathered_rows']} rows, expected {world * B_PER_GPU}")
-        line["multi_gpu_checks"] = "ok" if not bad else bad
-        print(json.dumps(line), flush=True)
-    if distributed:
-        dist.barrier()                      # rank 0 measured the roofline leg alone; leave together
-        dist.destroy_process_group()
-    if rank == 0 and bad:
-        raise SystemExit("bench.py: multi-GPU consistency checks failed: " + "; ".join(bad))
+    return {"elapsed_eval": elapsed_eval, "slab_gathers_eval": slab_gathers_eval, "gather_us": gather_us,
+            "elapsed_fast": elapsed_fast, "info_fast": info_fast, "roof": roof, "roof_extra": roof_extra,
+            "ess_trained": ess_trained, "ess_trained_fast": ess_trained_fast, "spline3": spline3,
+            "trainer_row": trainer_row}
 
 
 if __name__ == "__main__":

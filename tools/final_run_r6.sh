@@ -5,8 +5,8 @@ set -x
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/final_r6; mkdir -p $O
 export TMPDIR=/tmp
-timeout 600 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json      # first: what the driver's round-end run sees (a fresh box)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_prof.log 2>&1
+timeout 600 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json      # first: every row of the bench line, on a fresh box
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_prof.log 2>&1
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv; rm -rf $O/prof
 bash tools/trace_trainer.sh > /dev/null 2>&1
 cp gpurun_out/trace_trainer/kernel_stats.csv $O/trainer_kernel_stats_rocprofv3.csv
@@ -17,8 +17,8 @@ bash tools/pmc_traffic.sh k_hmc_step_r4 $O/pmc_traffic_r4 3 > $O/pmc_traffic_r4.
 ITERS=2 PROF_SCRIPT=tools/bench_trainer.py bash tools/pmc_traffic.sh k_flow_log_prob_tape_r8 $O/pmc_tape > $O/pmc_tape.log 2>&1; cp $O/pmc_tape/summary.json $O/tape_r8_traffic_pmc_summary.json
 ITERS=2 PROF_SCRIPT=tools/bench_trainer.py bash tools/pmc_traffic.sh k_pgrad_tiles $O/pmc_pgrad > $O/pmc_pgrad.log 2>&1; cp $O/pmc_pgrad/summary.json $O/pgrad_tiles_traffic_pmc_summary.json
 rm -rf $O/pmc_traffic_r4 $O/pmc_tape $O/pmc_pgrad
-timeout 300 python bench.py --workload cfg4 --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/bench_cfg4_1gpu.json
-FABHIP_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_2ranks_one_gpu_gloo.json
+timeout 300 python bench.py --workload cfg4 --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/bench_cfg4_1gpu.json
+FABHIP_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_2ranks_one_gpu_gloo.json
 python tools/time_hmc_shapes.py 2>/dev/null | grep "W=" > $O/hmc_tile_shapes.txt
 python tools/timeline_r8.py 2048 2>/dev/null | tail -11 > $O/hmc_r8f_stage_timeline.txt
 timeout 300 python tools/bench_spline.py 2>/dev/null | tail -1 > $O/spline_cfg3.json

@@ -16,12 +16,12 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -3 "$OUT/pytest_gpu.log"
 fi
 
-timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
 
 # kernel trace + stats of the same command (CPU baseline leg skipped: it launches no kernels)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
-    python bench.py --no-cpu-baseline > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
+    python bench.py --full --no-cpu-baseline > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
 
 # PMC passes, each in its own run (never combined with a trace domain)
 i=0

@@ -19,7 +19,7 @@ for WL in headline cfg4; do
       continue
     fi
     LOG="$OUT/bench_${WL}_n${N}"
-    timeout -k 10 900 python bench.py --gpus $N --workload $WL --steps 30 --warmup 10 --no-cpu-baseline > "$LOG.json" 2> "$LOG.err"
+    timeout -k 10 900 python bench.py --gpus $N --workload $WL --steps 30 --warmup 10 --full --no-cpu-baseline > "$LOG.json" 2> "$LOG.err"
     RC=$?
     python - "$LOG.json" "$WL" "$N" "$RC" <<'PY' | tee -a "$OUT/table.txt"
 import json, sys
