@@ -84,6 +84,11 @@ TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
 _lib = None
 _lock = threading.Lock()
 
+class SmcArgs(C.Structure):       # fabhip_smc_args
+    _fields_ = [("enabled", C.c_int32), ("only_resample", C.c_int32), ("tau", C.c_double), ("u", C.c_void_p),
+                ("resampled", C.c_void_p), ("ess", C.c_void_p), ("ancestors", C.c_void_p), ("log_w_pre", C.c_void_p)]
+
+
 # every symbol include/fabhip.h declares (checked by tests/test_cabi_and_host.py)
 SYMBOLS = [
     "fabhip_strerror", "fabhip_version", "fabhip_flow_packed_floats", "fabhip_flow_pack", "fabhip_flow_sample",
@@ -107,8 +112,9 @@ SYMBOLS = [
     "fabhip_metropolis_partials_floats", "fabhip_metropolis_adapt_gathered",
     "fabhip_flow_pack_train", "fabhip_flow_log_prob_tape_rows", "fabhip_train_step_workspace_bytes", "fabhip_buffer_train_step",
     "fabhip_buffer_add", "fabhip_buffer_sample_workspace_bytes", "fabhip_buffer_sample",
+    "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
 ]
-ABI_VERSION = 216          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 217          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -136,6 +142,13 @@ def _declare(lib):
     lib.fabhip_ais_workspace_bytes.argtypes = [i64, i32, i32]
     lib.fabhip_ais_run.argtypes = [C.POINTER(AisArgs), vp]
     lib.fabhip_ais_phase.argtypes = [C.POINTER(AisArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_ais_smc_workspace_bytes.restype = sz
+    lib.fabhip_ais_smc_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.fabhip_ais_run_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), vp]
+    lib.fabhip_ais_phase_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_smc_workspace_bytes.restype = sz
+    lib.fabhip_smc_workspace_bytes.argtypes = [i64]
+    lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fabhip_hmc_partials_floats.restype = i64
     lib.fabhip_hmc_partials_floats.argtypes = [i64]
     lib.fabhip_hmc_adapt_gathered.argtypes = [vp, i32, i64, vp, vp, C.c_float, i32, vp, vp, vp]

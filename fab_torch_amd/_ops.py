@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 216          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 217          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM = 1, 2
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -244,6 +244,11 @@ def _register_fakes():
     @rf("fabhip::resample_systematic")
     def _(log_w, u0, n_samples):
         return log_w.new_empty((n_samples,), dtype=torch.int64)
+
+    @rf("fabhip::smc_decide")
+    def _(log_w, tau, u):
+        return (log_w.new_empty((log_w.shape[0],), dtype=torch.int64), log_w.new_empty((1,), dtype=torch.int32),
+                log_w.new_empty((1,)), log_w.new_empty((1,)))
 
     @rf("fabhip::resample_multinomial")
     def _(log_w, u):

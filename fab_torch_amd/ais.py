@@ -33,12 +33,36 @@ class LoggingInfo(NamedTuple):
     log_Z: float
 
 
+def check_noise_r(noise_r: torch.Tensor, M: int) -> torch.Tensor:
+    """The uniforms of the resampling steps: ONE float64 in [0, 1) per transition, `[M]` (the device clamps a value outside the
+    range to 0; the host does not read the values)."""
+    if not torch.is_tensor(noise_r) or noise_r.dtype != torch.float64 or tuple(noise_r.shape) != (int(M),):
+        got = (tuple(noise_r.shape), noise_r.dtype) if torch.is_tensor(noise_r) else type(noise_r).__name__
+        raise _ops.FabhipError(f"noise_r must be a float64 tensor of shape [{int(M)}] (one uniform per transition), got {got}")
+    return noise_r.contiguous()
+
+
+def _check_threshold(tau):
+    if tau is None:
+        return None
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or tau != tau:
+        raise _ops.FabhipError(f"resample_threshold must be None (plain AIS) or a number (ESS fraction), got {tau!r}")
+    return float(tau)
+
+
 class AnnealedImportanceSampler:
+    """`resample_threshold` (SMC mode, default None = plain AIS): before every transition the ESS of the current log-weights is
+    computed on the device; below the threshold the chains are resampled in proportion to their weights (systematic, on the
+    fixed-point CDF of `resample_systematic`) and continue with equal weights whose logsumexp is unchanged, so `log_Z`, the FAB
+    loss and the buffer see an ordinary `(point, log_w)`.  > 1: before every transition; 0: never (the decision still runs)."""
+
     def __init__(self, base_distribution, target_log_prob, transition_operator: TransitionOperator,
                  p_target: bool, alpha: Optional[float] = None, n_intermediate_distributions: int = 1,
-                 distribution_spacing_type: str = "linear"):
+                 distribution_spacing_type: str = "linear", resample_threshold: Optional[float] = None):
         if not p_target:
             assert alpha is not None, "Must specify alpha if AIS target is not p."
+        self.resample_threshold = resample_threshold
+        self.last_smc = None              # (resampled [M], ess [M], ancestors [M, B], log_w_pre [M, B]) of the last fused call
         self.base_distribution = base_distribution
         self.target_log_prob = target_log_prob
         self.transition_operator = transition_operator
@@ -50,8 +74,23 @@ class AnnealedImportanceSampler:
         self._logging_info: LoggingInfo
         self._last_stats = None
 
+    @property
+    def resample_threshold(self) -> Optional[float]:
+        return self.__dict__.get("_resample_threshold")      # (None for a sampler restored from a state that predates the setting)
+
+    @resample_threshold.setter
+    def resample_threshold(self, tau):
+        self.__dict__["_resample_threshold"] = _check_threshold(tau)
+
+    def _refuse_resampling(self, what: str):
+        if self.resample_threshold is not None:
+            raise _ops.FabhipError(f"resample_threshold={self.resample_threshold} (SMC mode) is not available for {what}: "
+                                   "set resample_threshold=None, or use a RealNVP / generic base distribution")
+
     def get_logging_info(self) -> Dict[str, Any]:
         info = self._logging_info._asdict()
+        if self.resample_threshold is not None and self.__dict__.get("_smc_info") is not None:
+            info.update(self._smc_info)                     # n_resampled, ess_min_in_chain of the last logged call
         info.update(self.transition_operator.get_logging_info())
         return info
 
@@ -93,6 +132,7 @@ class AnnealedImportanceSampler:
     def _run_spline(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None):
         """`run` for the spline family: ONE op call (torch.ops.fabhip.spline_ais_run).  `eps0` / `u0` [B, D]: the normal /
         uniform draws of the flow's base sample."""
+        self._refuse_resampling("the fused spline-flow call")
         ops = _ops.load()
         flow, target = self._spline_parts()
         op = self.transition_operator
@@ -114,8 +154,11 @@ class AnnealedImportanceSampler:
         x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw = out
         return Point(x, lq, lp, gq, gp), log_w, n_valid, stats, base_x, base_lw
 
-    def run(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None):
-        """(`u0` [B, D]: the uniform base draws of the SPLINE flow; an error for any other base distribution.)
+    def run(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None, noise_r=None,
+            trace: bool = False):
+        """(`noise_r` [M] float64: the uniforms of the resampling steps, SMC mode only; `trace`: keep the ancestors and the
+        log-weights every decision saw in `last_smc`.)
+        (`u0` [B, D]: the uniform base draws of the SPLINE flow; an error for any other base distribution.)
         Enqueue one AIS call; returns device tensors (Point fields sized [batch_size], log_w, n_valid[2],
         stats[16], base_x, base_log_w) without synchronising.  `want_base`: also return the chains' starting points
         after the "chain init" filtering and their log p - log q (generate_eval_data, ais.py:152-166)."""
@@ -151,18 +194,29 @@ class AnnealedImportanceSampler:
             assert noise_a.shape == (M, n_inner, B, D) and noise_b.shape == (M, n_inner, B)
         betas = self._betas()
         alpha = float(self.alpha) if self.alpha is not None else 0.0
+        tau = self.resample_threshold
+        if noise_r is not None:
+            if tau is None:
+                raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
+            noise_r = check_noise_r(noise_r, M)
+        # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
+        call = ops.ais_run if tau is None else ops.ais_run_smc
+        smc = () if tau is None else (tau, noise_r, bool(trace))
         if hmc:
-            out = ops.ais_run(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
-                              _ops.TRANSITION_HMC, eps0, noise_a, noise_b, op.epsilons, op.common_epsilon,
-                              op.mass_vector, n_inner, op.L, float(op.max_grad), float(op.target_p_accept),
-                              not op.eval_mode, op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last,
-                              bool(want_base), _ops.precision_of(flow))
+            out = call(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
+                       _ops.TRANSITION_HMC, eps0, noise_a, noise_b, op.epsilons, op.common_epsilon,
+                       op.mass_vector, n_inner, op.L, float(op.max_grad), float(op.target_p_accept),
+                       not op.eval_mode, op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last,
+                       bool(want_base), _ops.precision_of(flow), *smc)
         else:
-            out = ops.ais_run(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
-                              _ops.TRANSITION_METROPOLIS, eps0, noise_a, noise_b, op.noise_scalings, None, None,
-                              n_inner, 0, 0.0, float(op.target_prob_accept),
-                              bool(op.adjust_step_size and not op.eval_mode), None, None, None, None, bool(want_base),
-                              _ops.precision_of(flow))
+            out = call(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
+                       _ops.TRANSITION_METROPOLIS, eps0, noise_a, noise_b, op.noise_scalings, None, None,
+                       n_inner, 0, 0.0, float(op.target_prob_accept),
+                       bool(op.adjust_step_size and not op.eval_mode), None, None, None, None, bool(want_base),
+                       _ops.precision_of(flow), *smc)
+        if tau is not None:
+            self.last_smc = tuple(out[10:14])
+            out = out[:10]
         x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw = out
         point = Point(x, lq, lp, gq if hmc else None, gp if hmc else None)
         return point, log_w, n_valid, stats, base_x, base_lw
@@ -269,8 +323,20 @@ class AnnealedImportanceSampler:
         return isinstance(self.base_distribution, RealNVP) and \
             _owner_or_none(self.target_log_prob, _NativeTarget) is not None and self.transition_operator.is_native
 
+    def _resample_generic(self, point: Point, log_w: torch.Tensor, u: torch.Tensor, record: list):
+        """The resampling step of the generic path: the decision op (fabhip::smc_decide - the fused call's own kernel) + the
+        existing row gather; no host synchronisation (the gather runs with identity ancestors when nothing is resampled)."""
+        ops = _ops.load()
+        log_w = log_w.contiguous()
+        anc, flag, ess, common = ops.smc_decide(log_w, float(self.resample_threshold), u)
+        g = lambda t: None if t is None else ops.gather_rows(t.detach().contiguous().float().view(t.shape[0], -1),      # noqa: E731
+                                                             anc).view(t.shape)
+        point = Point(g(point.x), g(point.log_q), g(point.log_p), g(point.grad_log_q), g(point.grad_log_p))
+        record.append((flag, ess, anc, log_w))
+        return point, torch.where(flag.bool(), common, log_w)
+
     def _sample_generic(self, batch_size: int, logging: bool, noise_a=None, noise_b=None, want_base: bool = False,
-                        raise_at_end: bool = True):
+                        raise_at_end: bool = True, noise_r=None):
         """ais.py:53-105 for ANY `Distribution` / `LogProbFunc` plug-ins (fab/types_.py:5-27): the reference's loop,
         stepped from Python; the plug-ins evaluate their own densities, the transitions / log-weight arithmetic /
         ESS run as fabhip kernels (transition_operators.py: generic path).  Explicit noise (parity replays): after the
@@ -293,7 +359,13 @@ class AnnealedImportanceSampler:
         ess_base = ops.ess_logz((point.log_p - point.log_q).contiguous(), None, 1.0)
         hmc = isinstance(op, HamiltonianMonteCarlo)
         n_inner = op.n_outer if hmc else op.n_updates
+        smc_on, record = self.resample_threshold is not None, []
+        if smc_on:                                          # (drawn after the plug-ins' own draws of the chain initialisation)
+            noise_r = (torch.rand(M, dtype=torch.float64, device=log_w.device) if noise_r is None
+                       else check_noise_r(noise_r, M).to(log_w.device))
         for j in range(1, M + 1):
+            if smc_on:
+                point, log_w = self._resample_generic(point, log_w, noise_r[j - 1:j], record)
             n = point.x.shape[0]
             beta, beta_next = float(self.B_space[j]), float(self.B_space[j + 1])
             lw = log_w if beta_next != beta else None                              # ais.py:93
@@ -304,9 +376,13 @@ class AnnealedImportanceSampler:
             else:
                 point = op.transition(point, j, beta, log_w=lw, beta_next=beta_next, noise_x=na, noise_u=nb)
         point, log_w = self._remove_nan_and_infs(point, log_w, "chain end", raise_exception=raise_at_end)
+        if smc_on:
+            self.last_smc = (torch.cat([r[0] for r in record]), torch.cat([r[1] for r in record]),
+                             torch.stack([r[2] for r in record]).int(), torch.stack([r[3] for r in record]))
         if logging:
             st = torch.cat([ess_base[:1], ops.ess_logz(log_w.contiguous(), None, float(B))[:2]]).tolist()
             self._logging_info = LoggingInfo(ess_base=st[0], ess_ais=st[1], log_Z=st[2])
+            self._log_smc()
         if want_base:
             return point, log_w.detach(), base
         return point, log_w.detach()
@@ -328,9 +404,22 @@ class AnnealedImportanceSampler:
         g = lambda t: None if t is None else t[keep].contiguous()      # noqa: E731
         return Point(g(point.x), g(point.log_q), g(point.log_p), g(point.grad_log_q), g(point.grad_log_p)), g(log_w)
 
+    def _log_smc(self):
+        """n_resampled / ess_min_in_chain of the call that just ended (SMC mode only): one more small read, after the call's own."""
+        self.__dict__["_smc_info"] = None
+        if self.resample_threshold is not None and self.last_smc is not None:
+            flag, ess = self.last_smc[0], self.last_smc[1]
+            h = torch.stack([flag.float().sum(), ess.min()]).tolist()
+            self.__dict__["_smc_info"] = {"n_resampled": int(h[0]), "ess_min_in_chain": float(h[1])}
+
     def sample_and_log_weights(self, batch_size: int, logging: bool = True, eps0=None, noise_a=None, noise_b=None,
-                               u0=None) -> Tuple[Point, torch.Tensor]:
+                               u0=None, noise_r=None) -> Tuple[Point, torch.Tensor]:
         fused_spline = self._spline_parts() is not None
+        smc_on = self.resample_threshold is not None
+        if fused_spline:
+            self._refuse_resampling("the fused spline-flow call")
+        if noise_r is not None and not smc_on:
+            raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
         if u0 is not None and not fused_spline:               # (ADVICE r3: it used to be dropped silently)
             raise _ops.FabhipError("u0 (uniform base draws) belongs to the fused spline-flow call: this sampler's base "
                                    "distribution / transition operator does not take that path")
@@ -338,9 +427,10 @@ class AnnealedImportanceSampler:
             if eps0 is not None:
                 raise _ops.FabhipError("eps0 is the base noise of a fab_torch_amd RealNVP; a generic base_distribution "
                                        "draws its own samples in sample_and_log_prob")
-            return self._sample_generic(batch_size, logging, noise_a, noise_b)
+            return self._sample_generic(batch_size, logging, noise_a, noise_b, noise_r=noise_r)
         repeated = None
-        if (not fused_spline and self.prefetch and eps0 is None and noise_a is None and noise_b is None
+        # (SMC mode: the prefetch of repeated calls is bypassed - its second piece runs through the plain phase op)
+        if (not fused_spline and not smc_on and self.prefetch and eps0 is None and noise_a is None and noise_b is None
                 and isinstance(self.transition_operator, HamiltonianMonteCarlo)):
             flow, target = self._native_parts()
             op = self.transition_operator
@@ -358,7 +448,10 @@ class AnnealedImportanceSampler:
             if fused_spline:
                 point, log_w, n_valid, stats, _, _ = self._run_spline(batch_size, eps0, noise_a, noise_b, u0=u0)
             else:
-                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b)
+                if smc_on:
+                    self._pf_take(None)                                          # (a piece prefetched before the mode was set)
+                    self.__dict__.pop("_pf_last_key", None)
+                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b, noise_r=noise_r)
             host, (n_init, n_end) = _ops.read_counts_and_stats(n_valid, stats)   # the single device->host read
         if n_init == 0:
             raise NoValidPoints("init")
@@ -370,6 +463,7 @@ class AnnealedImportanceSampler:
         st = host
         if logging:
             self._logging_info = LoggingInfo(ess_base=float(st[0]), ess_ais=float(st[3]), log_Z=float(st[4]))
+            self._log_smc()
         return point, log_w.detach()
 
     def generate_eval_data(self, outer_batch_size: int, inner_batch_size: int):

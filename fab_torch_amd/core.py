@@ -29,8 +29,9 @@ SUPPORTED_LOSSES = [None, "fab_alpha_div", "forward_kl", "flow_reverse_kl", "flo
 class FABModel:
     def __init__(self, flow, target_distribution, n_intermediate_distributions: int, alpha: float = 2.,
                  transition_operator: Optional[TransitionOperator] = None, ais_distribution_spacing: str = "linear",
-                 loss_type: Optional[str] = None, use_ais: bool = True):
+                 loss_type: Optional[str] = None, use_ais: bool = True, ais_resample_threshold: Optional[float] = None):
         assert loss_type in SUPPORTED_LOSSES
+        self.ais_resample_threshold = ais_resample_threshold       # SMC mode of the sampler (ais.py), None: plain AIS
         if loss_type in EXPERIMENTAL_LOSSES:               # same refusal as the reference (core.py:50-51)
             raise Exception("Running using experiment loss not used within the main FAB paper.")
         if loss_type in ALPHA_DIV_TARGET_LOSSES:
@@ -53,7 +54,8 @@ class FABModel:
             base_distribution=self.flow, target_log_prob=self.target_distribution.log_prob,
             transition_operator=self.transition_operator, p_target=False, alpha=self.alpha,
             n_intermediate_distributions=self.n_intermediate_distributions,
-            distribution_spacing_type=self.ais_distribution_spacing)
+            distribution_spacing_type=self.ais_distribution_spacing,
+            resample_threshold=getattr(self, "ais_resample_threshold", None))
 
     def parameters(self):
         return self.flow.parameters()

@@ -1064,6 +1064,57 @@ __global__ void k_compact_copyback(CompactK a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// SMC mode: the gather of the point with the ancestors of k_smc_decide (reduce_resample.hip), through the compaction's staging
+// buffer and back.  Both kernels are always launched and read the device flag: the host's launch sequence is fixed.
+// ------------------------------------------------------------------------------------------------
+struct SmcGatherK {
+    PointDev pt;
+    float* log_w;
+    float* tmp;            // [B][3D+4]
+    const int* anc;        // [B]
+    const int* flag;
+    const float* lw_common;
+    const int* n_ptr;
+    long B;
+    int D;
+};
+
+__global__ void k_smc_gather(SmcGatherK a) {
+    if (*a.flag == 0) return;
+    long n0 = *a.n_ptr;
+    n0 = n0 < 0 ? 0 : (n0 > a.B ? a.B : n0);
+    const int D = a.D, RW = 3 * D + 4;
+    const bool hg = a.pt.gq != nullptr;
+    for (long r = blockIdx.x; r < n0; r += gridDim.x) {
+        long s = a.anc[r];
+        s = s < 0 ? 0 : (s >= n0 ? n0 - 1 : s);
+        float* o = a.tmp + r * RW;
+        for (int j = threadIdx.x; j < D; j += blockDim.x) {
+            o[j] = a.pt.x[s * D + j];
+            if (hg) { o[D + j] = a.pt.gq[s * D + j]; o[2 * D + j] = a.pt.gp[s * D + j]; }
+        }
+        if (threadIdx.x == 0) { o[3 * D] = a.pt.lq[s]; o[3 * D + 1] = a.pt.lp[s]; }
+    }
+}
+
+__global__ void k_smc_copyback(SmcGatherK a) {
+    if (*a.flag == 0) return;
+    long n0 = *a.n_ptr;
+    n0 = n0 < 0 ? 0 : (n0 > a.B ? a.B : n0);
+    const int D = a.D, RW = 3 * D + 4;
+    const bool hg = a.pt.gq != nullptr;
+    const float lw = *a.lw_common;
+    for (long r = blockIdx.x; r < n0; r += gridDim.x) {
+        const float* o = a.tmp + r * RW;
+        for (int j = threadIdx.x; j < D; j += blockDim.x) {
+            a.pt.x[r * D + j] = o[j];
+            if (hg) { a.pt.gq[r * D + j] = o[D + j]; a.pt.gp[r * D + j] = o[2 * D + j]; }
+        }
+        if (threadIdx.x == 0) { a.pt.lq[r] = o[3 * D]; a.pt.lp[r] = o[3 * D + 1]; a.log_w[r] = lw; }
+    }
+}
+
 __global__ void k_sub(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = a[i] - b[i];
 }
@@ -1674,11 +1725,25 @@ int fabhip_spline_ais_run(const fabhip_spline_ais_args* a, fabhip_stream_t strea
 
 int fabhip_ais_run(const fabhip_ais_args* a, fabhip_stream_t stream) {
     if (!a) return FABHIP_EINVAL;
-    return fabhip_ais_phase(a, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+    return fabhip_ais_phase_smc(a, nullptr, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
 }
 
 int fabhip_ais_phase(const fabhip_ais_args* a, int32_t phases, int32_t j_begin, int32_t j_end, float* partials,
                      fabhip_stream_t stream) {
+    return fabhip_ais_phase_smc(a, nullptr, phases, j_begin, j_end, partials, stream);
+}
+
+size_t fabhip_ais_smc_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner) {
+    return fabhip_ais_workspace_bytes(B, dim, n_inner) + align256((size_t)B * 8) + align256((size_t)B * 4) + 256;
+}
+
+int fabhip_ais_run_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, fabhip_stream_t stream) {
+    if (!a) return FABHIP_EINVAL;
+    return fabhip_ais_phase_smc(a, smc, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+}
+
+int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin, int32_t j_end,
+                         float* partials, fabhip_stream_t stream) {
     if (!a || !a->flow.packed || !a->betas || !a->step_state || !a->log_w ||
         !a->n_valid || !a->stats || !a->workspace || a->B < 1 || a->M < 1 || a->n_inner < 1)
         return FABHIP_EINVAL;
@@ -1694,7 +1759,11 @@ int fabhip_ais_phase(const fabhip_ais_args* a, int32_t phases, int32_t j_begin, 
     FAB_TRY(check_flow_shape(a->flow.dim, a->flow.n_layers, a->flow.width));
     FAB_TRY(check_target(&a->target, a->flow.dim));
     FAB_TRY(check_point(a->point, hmc));
-    if (a->workspace_bytes < fabhip_ais_workspace_bytes(a->B, a->flow.dim, a->n_inner)) return FABHIP_ENOSPC;
+    const bool smc_on = smc && smc->enabled != 0;
+    if (smc_on && partials) return FABHIP_ENOTSUP;
+    if (smc_on && j_begin <= j_end && !smc->u) return FABHIP_EINVAL;                  // (like the noise: read by the transitions only)
+    if (a->workspace_bytes < (smc_on ? fabhip_ais_smc_workspace_bytes(a->B, a->flow.dim, a->n_inner)
+                                     : fabhip_ais_workspace_bytes(a->B, a->flow.dim, a->n_inner))) return FABHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     const FlowDims f = flow_dims_of(a->flow);
     const TargetDev tg = make_target_dev(a->target);
@@ -1722,6 +1791,17 @@ int fabhip_ais_phase(const fabhip_ais_args* a, int32_t phases, int32_t j_begin, 
     if (ticket && !ws_kept) {
         if (j_begin > j_end) ticket = nullptr;
         else if (hipMemsetAsync(ticket, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
+    }
+    // scratch of the SMC step, behind the plain call's layout (which it leaves as it is)
+    unsigned long long* smc_cdf = nullptr;
+    int *smc_anc = nullptr, *smc_flag = nullptr;
+    float* smc_lw = nullptr;
+    if (smc_on) {
+        char* p = (char*)a->workspace + fabhip_ais_workspace_bytes(B, D, a->n_inner);
+        smc_cdf = (unsigned long long*)p; p += align256((size_t)B * 8);
+        smc_anc = (int*)p; p += align256((size_t)B * 4);
+        smc_flag = (int*)p;
+        smc_lw = (float*)(p + 64);
     }
 
     if (do_init) {
@@ -1760,6 +1840,26 @@ int fabhip_ais_phase(const fabhip_ais_args* a, int32_t phases, int32_t j_begin, 
         fabhip_anneal_coefs(a->betas[j + 1], a->alpha, a->p_target, &cn);
         float* lw = (a->betas[j + 1] != a->betas[j]) ? a->log_w : nullptr;      // ais.py:93
         const size_t nslab = (size_t)(j - 1) * a->n_inner;
+        if (smc_on) {
+            // resampling step of transition j (log_w targets the distribution this transition leaves invariant): decision,
+            // gather into the staging buffer, copy back - three launches whatever the decision.  No transition kernel keeps
+            // per-chain state in the workspace from one transition to the next (part_* / row_* / the proposal buffer are
+            // written and consumed inside one transition), so the point and log_w are all there is to move.
+            SmcK k;
+            k.log_w = a->log_w; k.n_ptr = a->n_valid; k.B = B; k.tau = smc->tau; k.u = smc->u + (j - 1);
+            k.cdf = smc_cdf; k.anc = smc_anc; k.flag = smc_flag; k.lw_common = smc_lw;
+            k.resampled_out = smc->resampled ? smc->resampled + (j - 1) : nullptr;
+            k.ess_out = smc->ess ? smc->ess + (j - 1) : nullptr;
+            k.anc_out = smc->ancestors ? smc->ancestors + (size_t)(j - 1) * B : nullptr;
+            k.lw_pre_out = smc->log_w_pre ? smc->log_w_pre + (size_t)(j - 1) * B : nullptr;
+            FAB_TRY(smc_decide(k, st));
+            SmcGatherK g{make_point_dev(a->point), a->log_w, tmp, smc_anc, smc_flag, smc_lw, a->n_valid, B, D};
+            const int grid = (int)(B < 4096 ? B : 4096);
+            hipLaunchKernelGGL(k_smc_gather, dim3(grid), dim3(64), 0, st, g);
+            hipLaunchKernelGGL(k_smc_copyback, dim3(grid), dim3(64), 0, st, g);
+            FAB_TRY(check_launch());
+            if (smc->only_resample) continue;
+        }
         if (hmc) {
             fabhip_hmc_args h;
             h.flow = a->flow; h.target = a->target; h.point = a->point; h.B = B; h.n_valid = a->n_valid;

@@ -94,6 +94,27 @@ struct TailArgs {
 };
 int tail_small(const TailArgs& a, int* dest, hipStream_t st);
 
+// The decision of the SMC mode (include/fabhip.h: fabhip_smc_args; reduce_resample.hip: k_smc_decide), one workgroup: fixed-point
+// weights W of log_w[:n0] (the resampler's own exp_spec / fixed_weight), their integer CDF, ESS = (sum W)^2 / (n0 sum W^2) from
+// exact integer sums, the device flag `ESS < tau`, the common log-weight after resampling and the systematic ancestors of the
+// first n0 rows (identity where the flag is off, and for the rows beyond n0).
+struct SmcK {
+    const float* log_w;                // [B]
+    const int* n_ptr;                  // rows in use (device; null: B)
+    long B;
+    double tau;
+    const double* u;                   // device, the ONE uniform of this decision
+    unsigned long long* cdf;           // workspace [B]
+    int* anc;                          // [B] out
+    int* flag;                         // [1] out
+    float* lw_common;                  // [1] out
+    int* resampled_out;                // optional [1]
+    float* ess_out;                    // optional [1]
+    int* anc_out;                      // optional [B] (a second copy: the caller's record)
+    float* lw_pre_out;                 // optional [B]: log_w as the decision saw it
+};
+int smc_decide(const SmcK& a, hipStream_t st);
+
 // 4-chain tiles (flow_r4.h) pay when 16-chain tiles cannot fill the chip: up to 288 workgroups of 4 chains (B <= 1152); off in fast
 // mode (no bf16 variant).  FABHIP_OPT_TILE_SHAPE = 16 / 4 forces the choice (tests exercise both).  D <= 32 and hidden width <= 320
 // only (the other instantiations spill registers and are not compiled).  Used by the transitions, the chain initialisation and

@@ -1337,6 +1337,114 @@ static int build_fixed_cdf(const float* log_w, long n, const ScanWs& ws, hipStre
     return check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------
+// SMC mode of the fused AIS call: the decision in front of a transition (launch.h: SmcK).  A few thousand chains: ONE
+// workgroup reduces, scans and searches; the point is gathered grid-wide afterwards (ais_kernels.hip).  Every sum that decides
+// is an integer sum (associative: the same bits for any reduction order): sum W < 2^62 in 64 bits, sum W^2 < 2^98 in 128.
+// ------------------------------------------------------------------------------------------------
+constexpr int SMC_THREADS = 1024;
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_decide(SmcK a) {
+    __shared__ float sh_max[SMC_THREADS / 64];
+    __shared__ unsigned long long sh_w[SMC_THREADS / 64];
+    __shared__ unsigned long long sh_lo[SMC_THREADS], sh_hi[SMC_THREADS];
+    __shared__ unsigned long long sh_run;
+    __shared__ unsigned long long sh_S, sh_U;
+    __shared__ int sh_F, sh_fire;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    long n0 = a.n_ptr ? (long)*a.n_ptr : a.B;
+    n0 = n0 < 0 ? 0 : (n0 > a.B ? a.B : n0);
+    // 1. the maximum finite log-weight (0 when there is none: fixed_point_weights)
+    float mx = -INFINITY;
+    for (long i = tid; i < a.B; i += SMC_THREADS) {
+        const float v = a.log_w[i];
+        if (a.lw_pre_out) a.lw_pre_out[i] = v;
+        if (i < n0 && isfinite(v)) mx = fmaxf(mx, v);
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (lane == 0) sh_max[w] = mx;
+    if (tid == 0) sh_run = 0ull;
+    __syncthreads();
+    mx = sh_max[0];
+    for (int i = 1; i < SMC_THREADS / 64; ++i) mx = fmaxf(mx, sh_max[i]);
+    const bool any_finite = mx != -INFINITY;
+    if (!any_finite) mx = 0.f;
+    // 2. W, the inclusive CDF (chunks of 1024 rows with a running total) and sum W^2 as a 128-bit integer
+    unsigned long long acc_lo = 0ull, acc_hi = 0ull;
+    for (long base = 0; base < n0; base += SMC_THREADS) {
+        const long i = base + tid;
+        const unsigned long long q = i < n0 ? fixed_weight(a.log_w[i], mx) : 0ull;
+        const unsigned long long lo = q * q, hi = __umul64hi(q, q);
+        acc_lo += lo;
+        acc_hi += hi + (acc_lo < lo ? 1ull : 0ull);
+        unsigned long long inc = q;
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long t = shfl_up_u64(inc, off);
+            if (lane >= off) inc += t;
+        }
+        if (lane == 63) sh_w[w] = inc;
+        __syncthreads();
+        unsigned long long woff = 0ull, tot = 0ull;
+        for (int k = 0; k < SMC_THREADS / 64; ++k) { if (k < w) woff += sh_w[k]; tot += sh_w[k]; }
+        if (i < n0) a.cdf[i] = sh_run + woff + inc;
+        __syncthreads();
+        if (tid == 0) sh_run += tot;
+        __syncthreads();
+    }
+    sh_lo[tid] = acc_lo; sh_hi[tid] = acc_hi;
+    __syncthreads();
+    for (int s = SMC_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const unsigned long long l = sh_lo[tid] + sh_lo[tid + s];
+            sh_hi[tid] += sh_hi[tid + s] + (l < sh_lo[tid] ? 1ull : 0ull);
+            sh_lo[tid] = l;
+        }
+        __syncthreads();
+    }
+    // 3. the decision: one float64 expression in a fixed order (tests/smc_spec.py restates it)
+    if (tid == 0) {
+        const unsigned long long total = sh_run;
+        const double S1 = (double)total;
+        const double S2 = (double)sh_hi[0] * 18446744073709551616.0 + (double)sh_lo[0];
+        const double ess = total > 0ull ? (S1 * S1) / ((double)n0 * S2) : 0.0;
+        const int fire = (total > 0ull && ess < a.tau) ? 1 : 0;
+        double u0 = *a.u;
+        if (!(u0 >= 0.0 && u0 < 1.0)) u0 = 0.0;
+        const Strata m = make_strata(total, u0, n0 > 0 ? n0 : 1);
+        sh_S = m.S; sh_U = m.U; sh_F = m.F; sh_fire = fire;
+        *a.flag = fire;
+        // log of the mean weight: log_Z = logsumexp(log_w) - log(B) of the tail kernel is unchanged by the resampling
+        *a.lw_common = fire ? (float)((double)mx + log(S1 * 1.4551915228366852e-11 / (double)n0)) : 0.f;
+        if (a.resampled_out) *a.resampled_out = fire;
+        if (a.ess_out) *a.ess_out = (float)ess;
+    }
+    __syncthreads();
+    // 4. ancestors: first j with C[j] > t_k, t_k = (k S + U) >> F (oracle/numerical.py: systematic_fixed)
+    const bool fire = sh_fire != 0;
+    const unsigned long long S = sh_S, U = sh_U;
+    const int F = sh_F;
+    for (long k = tid; k < a.B; k += SMC_THREADS) {
+        long r = k;
+        if (fire && k < n0) {
+            const unsigned long long t = ((unsigned long long)k * S + U) >> F;
+            long lo = 0, hi = n0;                       // first index with cdf > t
+            while (lo < hi) {
+                const long mid = (lo + hi) >> 1;
+                if (a.cdf[mid] > t) hi = mid; else lo = mid + 1;
+            }
+            r = lo < n0 ? lo : n0 - 1;
+        }
+        a.anc[k] = (int)r;
+        if (a.anc_out) a.anc_out[k] = (int)r;
+    }
+}
+
+int smc_decide(const SmcK& a, hipStream_t st) {
+    if (!a.log_w || !a.u || !a.cdf || !a.anc || !a.flag || !a.lw_common || a.B < 1 || a.B > 0x7fffffffL) return FABHIP_EINVAL;
+    hipLaunchKernelGGL(k_smc_decide, dim3(1), dim3(SMC_THREADS), 0, st, a);
+    return check_launch();
+}
+
 int tail_small(const TailArgs& a, int* dest, hipStream_t st) {
     if (a.B > (long)TAIL_MAX_BLOCKS * ESS_THREADS * 4 || a.B < 1) return FABHIP_ENOTSUP;
     const int nb = grid_for(a.B, ESS_THREADS * 4, ESS_MAX_BLOCKS);          // fabhip_ess_logz's grid for the same row capacity
@@ -1493,6 +1601,20 @@ int fabhip_resample_systematic(const float* log_w, int64_t n, double u0, int64_t
         hipLaunchKernelGGL(k_emit_fill_runs, dim3(256), dim3(256), 0, st, giant_count, giant_desc, giant_cap,
                            (long long*)idx);
     return check_launch();
+}
+
+size_t fabhip_smc_workspace_bytes(int64_t B) { return al256((size_t)(B > 0 ? B : 0) * 8) + al256((size_t)(B > 0 ? B : 0) * 4) + 512; }
+
+int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
+                      int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
+                      size_t workspace_bytes, fabhip_stream_t stream) {
+    if (!log_w || !u || !ancestors || !resampled || !log_w_common || !workspace || B < 1) return FABHIP_EINVAL;
+    if (workspace_bytes < fabhip_smc_workspace_bytes(B)) return FABHIP_ENOSPC;
+    SmcK k;
+    k.log_w = log_w; k.n_ptr = n_ptr; k.B = (long)B; k.tau = tau; k.u = u;
+    k.cdf = (unsigned long long*)workspace; k.anc = ancestors; k.flag = resampled; k.lw_common = log_w_common;
+    k.resampled_out = nullptr; k.ess_out = ess; k.anc_out = nullptr; k.lw_pre_out = log_w_pre;
+    return smc_decide(k, (hipStream_t)stream);
 }
 
 int fabhip_gather_rows(const float* src, const int64_t* idx, float* dst, int64_t n_out, int64_t row_len,

@@ -846,15 +846,33 @@ void metropolis_generic_accept(const Tensor& x_new, const Tensor& new_lq, const 
 //   (x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid int32[2], stats float[16], base_x, base_log_w)
 // grad_* are empty for Metropolis, base_* are empty unless want_base.
 // ------------------------------------------------------------------------------------------------------------------
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run(
+// SMC mode of the AIS ops (fabhip_smc_args): `tau` absent = the plain call through the same entry points.  noise_r [M] float64
+// (absent: drawn from the default generator AFTER the transition noise); the per-transition records are allocated here.
+struct SmcOp {
+    optional<double> tau;
+    optional<Tensor> noise_r;
+    bool want_trace = false;
+    Tensor resampled, ess, ancestors, log_w_pre, u;     // out (ais_run_smc)
+};
+
+static Tensor smc_uniforms(const optional<Tensor>& noise_r, int64_t M, const Tensor& like) {
+    if (!noise_r.has_value()) return at::rand({M}, like.options().dtype(at::kDouble));
+    need(*noise_r, at::kDouble, "noise_r");
+    TORCH_CHECK(noise_r->dim() == 1 && noise_r->numel() == M && noise_r->is_contiguous() && noise_r->device() == like.device(),
+                "fabhip: noise_r must be a contiguous float64 tensor [M] on the call's device");
+    return *noise_r;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run_impl(
     const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
     const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
     bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
     const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
     int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
     optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision) {
+    int64_t precision, SmcOp* smc) {
     c10::DeviceGuard g(eps0.device());
+    const bool smc_on = smc != nullptr && smc->tau.has_value();
     // noise_a / noise_b absent: drawn HERE, from the default generator in the order the Python side draws them (normal
     // [M, n_inner, B, dim], then exponential(1) / uniform [M, n_inner, B]) - but AFTER the chain initialisation is enqueued, so the
     // device works while the host launches the draws (FABHIP_AIS_CONTINUE)
@@ -915,20 +933,85 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     a.avg_distance_last = fpmn_opt(avg_distance_last, 1, eps0, "avg_distance_last", true);
     a.base_x = want_base ? base_x.data_ptr<float>() : nullptr;
     a.base_log_w = want_base ? base_lw.data_ptr<float>() : nullptr;
-    const size_t nb = fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
+    const size_t nb = smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
+                             : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
     Tensor ws = scratch(nb, eps0);
     a.workspace = aligned(ws); a.workspace_bytes = nb;
+    if (smc == nullptr) {                                      // the plain ops: the entry points they have always called
+        if (!draw_inside) {
+            chk(fabhip_ais_run(&a, stream_of(eps0)), "ais_run");
+        } else {
+            chk(fabhip_ais_phase(&a, FABHIP_AIS_INIT, 1, 0, nullptr, stream_of(eps0)), "ais_run (chain initialisation)");
+            noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
+            noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
+            a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
+            chk(fabhip_ais_phase(&a, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, stream_of(eps0)),
+                "ais_run (transitions)");
+        }
+        return {x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw};
+    }
+    fabhip_smc_args sa;
+    sa.enabled = smc_on ? 1 : 0; sa.only_resample = 0; sa.tau = smc_on ? *smc->tau : 0.0;
+    sa.u = nullptr; sa.resampled = nullptr; sa.ess = nullptr; sa.ancestors = nullptr; sa.log_w_pre = nullptr;
+    auto smc_outputs = [&]() {                                 // (after the transition noise: the generator's order of draws)
+        if (!smc_on) return;
+        smc->u = smc_uniforms(smc->noise_r, M, eps0);
+        smc->resampled = at::empty({M}, eps0.options().dtype(at::kInt));
+        smc->ess = fempty({M}, eps0);
+        sa.u = smc->u.data_ptr<double>(); sa.resampled = smc->resampled.data_ptr<int32_t>(); sa.ess = smc->ess.data_ptr<float>();
+        if (smc->want_trace) {
+            smc->ancestors = at::empty({M, B}, eps0.options().dtype(at::kInt));
+            smc->log_w_pre = fempty({M, B}, eps0);
+            sa.ancestors = smc->ancestors.data_ptr<int32_t>(); sa.log_w_pre = smc->log_w_pre.data_ptr<float>();
+        }
+    };
     if (!draw_inside) {
-        chk(fabhip_ais_run(&a, stream_of(eps0)), "ais_run");
+        smc_outputs();
+        chk(fabhip_ais_run_smc(&a, &sa, stream_of(eps0)), "ais_run_smc");
     } else {
-        chk(fabhip_ais_phase(&a, FABHIP_AIS_INIT, 1, 0, nullptr, stream_of(eps0)), "ais_run (chain initialisation)");
+        chk(fabhip_ais_phase_smc(&a, &sa, FABHIP_AIS_INIT, 1, 0, nullptr, stream_of(eps0)), "ais_run_smc (chain initialisation)");
         noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
         noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
         a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
-        chk(fabhip_ais_phase(&a, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, stream_of(eps0)),
-            "ais_run (transitions)");
+        smc_outputs();
+        chk(fabhip_ais_phase_smc(&a, &sa, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, stream_of(eps0)),
+            "ais_run_smc (transitions)");
     }
     return {x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run(
+    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
+    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
+    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
+    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
+    int64_t precision) {
+    return ais_run_impl(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0, noise_a_in,
+                        noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first,
+                        p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, nullptr);
+}
+
+// ais_run with the SMC mode: the ten outputs of ais_run, then resampled int32[M], ess float[M], ancestors int32[M, B],
+// log_w_pre float[M, B] (the last two empty unless want_trace; all four empty when tau is absent).
+std::vector<Tensor> ais_run_smc(
+    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
+    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
+    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
+    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
+    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace) {
+    SmcOp smc;
+    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace;
+    auto t = ais_run_impl(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, &smc);
+    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
+    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
+            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
+            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
 }
 
 // The same call in pieces (fabhip_ais_phase): the state tensors are the caller's, in/out across the phases of one AIS
@@ -946,7 +1029,7 @@ int64_t ais_phase_core(const Tensor& packed, int64_t dim, int64_t n_layers, int6
                optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
                optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
                optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision,
-               const std::string* group_name) {
+               const std::string* group_name, const fabhip_smc_args* smc = nullptr) {
     c10::DeviceGuard g(x.device());
     fabhip_ais_args a;
     a.flow = make_flow(packed, dim, n_layers, width, precision);
@@ -983,13 +1066,16 @@ int64_t ais_phase_core(const Tensor& packed, int64_t dim, int64_t n_layers, int6
     a.avg_distance_last = fpmn_opt(avg_distance_last, 1, x, "avg_distance_last", true);
     a.base_x = fpmn_opt(base_x, B * dim, x, "base_x");
     a.base_log_w = fpmn_opt(base_log_w, B, x, "base_log_w");
-    const size_t nb = fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
+    const size_t nb = (smc && smc->enabled) ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
+                                            : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
     Tensor ws = scratch(nb, x);
     a.workspace = aligned(ws); a.workspace_bytes = nb;
     float* slab = fpmn_opt(partials, hmc ? fabhip_hmc_partials_floats(B)
                                          : fabhip_metropolis_partials_floats(B, (int32_t)M, (int32_t)n_inner), x, "partials");
     if (group_name == nullptr) {
-        chk(fabhip_ais_phase(&a, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)), "ais_phase");
+        if (smc) chk(fabhip_ais_phase_smc(&a, smc, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)),
+                     "ais_phase_smc");
+        else chk(fabhip_ais_phase(&a, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)), "ais_phase");
         return 0;
     }
     // ---- one shard's tuned call: the loop fab_torch_amd/parallel.py stepped from Python in rounds 2 - 4 ----
@@ -1050,6 +1136,61 @@ void ais_phase(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t widt
                    j_end, eps0, noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
                    x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
                    avg_distance_first, avg_distance_last, base_x, base_log_w, precision, nullptr);
+}
+
+// ais_phase with the SMC mode: transition j's phase starts with its resampling step (`only_resample`: and ends there).  The
+// records are the caller's, [M] / [M, B]; only the rows of the transitions this call runs are written.
+void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+                   const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
+                   bool p_target, int64_t transition, int64_t phases, int64_t j_begin, int64_t j_end,
+                   const optional<Tensor>& eps0, const Tensor& noise_a, const Tensor& noise_b, Tensor step_state,
+                   optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
+                   double target_p_accept, bool tune, Tensor x, Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q,
+                   optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
+                   optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
+                   optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision,
+                   optional<double> tau, const optional<Tensor>& noise_r, bool only_resample, optional<Tensor> resampled,
+                   optional<Tensor> ess, optional<Tensor> ancestors, optional<Tensor> log_w_pre) {
+    const int64_t B = x.size(0), M = (int64_t)betas.size() - 2;
+    fabhip_smc_args sa;
+    sa.enabled = tau.has_value() ? 1 : 0; sa.only_resample = only_resample ? 1 : 0; sa.tau = tau.has_value() ? *tau : 0.0;
+    sa.u = nullptr; sa.resampled = nullptr; sa.ess = nullptr; sa.ancestors = nullptr; sa.log_w_pre = nullptr;
+    if (sa.enabled) {
+        TORCH_CHECK(noise_r.has_value(), "fabhip: ais_phase_smc needs noise_r (float64 [M]) when tau is given");
+        sa.u = smc_uniforms(noise_r, M, x).data_ptr<double>();
+        auto ints = [&](optional<Tensor>& t, int64_t n, const char* what) -> int32_t* {
+            if (!t.has_value()) return nullptr;
+            need(*t, at::kInt, what); need_n(*t, n, x, what);
+            return t->data_ptr<int32_t>();
+        };
+        sa.resampled = ints(resampled, M, "resampled");
+        sa.ancestors = ints(ancestors, M * B, "ancestors");
+        sa.ess = fpmn_opt(ess, M, x, "ess");
+        sa.log_w_pre = fpmn_opt(log_w_pre, M * B, x, "log_w_pre");
+    }
+    ais_phase_core(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, phases, j_begin,
+                   j_end, eps0, noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                   x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
+                   avg_distance_first, avg_distance_last, base_x, base_log_w, precision, nullptr, &sa);
+}
+
+// The decision of the SMC step alone (fabhip_smc_decide) for samplers that step their transitions from Python:
+// (ancestors int64[n] - gather_rows takes them as they are -, resampled int32[1], ess float[1], log_w_common float[1]).
+std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, double tau, const Tensor& u) {
+    c10::DeviceGuard g(log_w.device());
+    const int64_t n = log_w.numel();
+    TORCH_CHECK(n >= 1, "fabhip: smc_decide needs at least one chain");
+    need(u, at::kDouble, "u");
+    TORCH_CHECK(u.numel() == 1 && u.device() == log_w.device(), "fabhip: u must be ONE float64 on log_w's device");
+    Tensor anc = at::empty({n}, log_w.options().dtype(at::kInt)), flag = at::empty({1}, log_w.options().dtype(at::kInt));
+    Tensor ess = fempty({1}, log_w), common = fempty({1}, log_w);
+    const size_t nb = fabhip_smc_workspace_bytes(n);
+    Tensor ws = scratch(nb, log_w);
+    chk(fabhip_smc_decide(fp(log_w, "log_w"), n, nullptr, tau, u.data_ptr<double>(), anc.data_ptr<int32_t>(),
+                          flag.data_ptr<int32_t>(), ess.data_ptr<float>(), common.data_ptr<float>(), nullptr, aligned(ws), nb,
+                          stream_of(log_w)),
+        "smc_decide");
+    return {anc.to(at::kLong), flag, ess, common};
 }
 
 // One shard's WHOLE tuned AIS call in one op: chain initialisation, M x {HMC transition publishing its
@@ -1312,6 +1453,20 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "
           "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "
           "Tensor(q!)? base_log_w, int precision=0) -> ()");
+    m.def("ais_run_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
+          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
+          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
+          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
+          "Tensor? noise_r, bool want_trace) -> Tensor[]");
+    m.def("ais_phase_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
+          "int j_end, Tensor? eps0, Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, "
+          "Tensor? mass, int n_inner, int L, float max_grad, float target_p_accept, bool tune, Tensor(c!) x, "
+          "Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, Tensor(g!)? grad_log_p, Tensor(h!) log_w, "
+          "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "
+          "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "
+          "Tensor(q!)? base_log_w, int precision, float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
+          "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre) -> ()");
+    m.def("smc_decide(Tensor log_w, float tau, Tensor u) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("ais_sharded_tuned(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor? eps0, "
           "Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int L, "
           "float max_grad, float target_p_accept, Tensor(c!) x, Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, "
@@ -1389,6 +1544,9 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("metropolis_transition", metropolis_transition);
     m.impl("ais_run", ais_run);
     m.impl("ais_phase", ais_phase);
+    m.impl("ais_run_smc", ais_run_smc);
+    m.impl("ais_phase_smc", ais_phase_smc);
+    m.impl("smc_decide", smc_decide);
     m.impl("ais_sharded_tuned", ais_sharded_tuned);
     m.impl("metropolis_adapt_gathered", metropolis_adapt_gathered);
     m.impl("tape_gemm", tape_gemm);

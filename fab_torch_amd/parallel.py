@@ -90,6 +90,15 @@ def gather_particles(x, log_w, log_q, capacity: int, group=None, compact: bool =
     return buf[:, :D], buf[:, D], buf[:, D + 1]
 
 
+def refuse_resampling(who: str, threshold):
+    """The SMC mode resamples over ALL chains of a call; the sharded samplers keep every rank's chains to themselves until the
+    final gather, so a sampler with `resample_threshold` set is refused rather than resampled shard by shard."""
+    if threshold is not None:
+        from ._ops import FabhipError
+        raise FabhipError(f"{who}: resample_threshold={threshold} (SMC mode) is not available for sharded chains; "
+                          "set resample_threshold=None on the sampler")
+
+
 class ShardedAIS:
     """`sample_and_log_weights(total_batch)` over all ranks.
 
@@ -107,6 +116,7 @@ class ShardedAIS:
         world = dist.get_world_size(self.group) if dist.is_initialized() else 1
         rank = dist.get_rank(self.group) if dist.is_initialized() else 0
         sizes = shard_sizes(total_batch, world)
+        refuse_resampling("ShardedAIS", getattr(getattr(self.local_sampler, "__self__", None), "resample_threshold", None))
         x, log_w, log_q = self.local_sampler(sizes[rank])
         if self.sync_step_size and self.step_state is not None and world > 1:
             # ONE tiny all-reduce for all step-size tensors (epsilons [M, n_outer] + common_epsilon [1]: latency-bound)
@@ -356,8 +366,9 @@ class ShardedAnnealedImportanceSampler:
     def sample_and_log_weights(self, total_batch: int, eps0=None, noise_a=None, noise_b=None, compact: bool = True,
                                logging: bool = True):
         world = _world(self.group)
-        b = self.local_batch(total_batch)
         be = self.backend
+        refuse_resampling("ShardedAnnealedImportanceSampler", getattr(getattr(be, "ais", None), "resample_threshold", None))
+        b = self.local_batch(total_batch)
         self.n_slab_gathers = 0
         if world == 1 or not be.tuning:
             pt, log_w = be.run_fused(b, eps0, noise_a, noise_b)

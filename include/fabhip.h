@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 216
+#define FABHIP_ABI_VERSION 217
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -596,6 +596,46 @@ enum { FABHIP_AIS_INIT = 1, FABHIP_AIS_FINISH = 2,
                                       * transition noise while the device runs the chain initialisation). */
 int fabhip_ais_phase(const fabhip_ais_args* args, int32_t phases, int32_t j_begin, int32_t j_end, float* partials,
                      fabhip_stream_t stream);
+
+/* SMC mode (adaptive resampling inside the call; the sampler of Del Moral et al., AIS being its special case without
+ * resampling).  Before transition j = 1 .. M, with n0 = n_valid[0] chains in use:
+ *   W   = fixed-point weights of log_w[:n0] (the systematic resampler's: exp_spec(log_w - max) 2^36, non-finite rows 0),
+ *   ess = (sum W)^2 / (n0 sum W^2)        (integer sums, one float64 expression; sum W == 0: no resampling),
+ *   ess < tau: ancestors = the systematic resampler's indices for u[j - 1] on that CDF; x, log q, log p (HMC: and both
+ *              gradients) of the first n0 rows are gathered with them and every log_w[:n0] becomes
+ *              max + log(sum W 2^-36 / n0), so that logsumexp(log_w) - and with it log Z - is what it was;
+ *   else the step is the identity.
+ * Decided and executed on the device: the launch sequence does not depend on the outcome, the host never waits.
+ * `enabled` == 0 (or a NULL fabhip_smc_args): the plain call, launch for launch.  The outputs may each be NULL. */
+typedef struct {
+    int32_t enabled;
+    int32_t only_resample;    /* != 0: run the resampling steps of j_begin .. j_end WITHOUT their transitions (tests read the
+                                 point between the two halves of a phase)                                                     */
+    double tau;               /* threshold on ess in [1/n0, 1]; > 1: always, <= 0: never                                       */
+    const double* u;          /* device [M], one uniform in [0, 1) per transition (outside the range: taken as 0); read by the
+                                 transitions only - a call without transitions (FABHIP_AIS_INIT alone) may pass NULL            */
+    int32_t* resampled;       /* device [M]: 1 where transition j was preceded by a resampling                                 */
+    float* ess;               /* device [M]: the ess the decision saw                                                          */
+    int32_t* ancestors;       /* device [M][B]: row k of the point came from row ancestors[j-1][k] (identity: no resampling)   */
+    float* log_w_pre;         /* device [M][B]: log_w as the decision saw it                                                   */
+} fabhip_smc_args;
+
+/* fabhip_ais_workspace_bytes + the scratch of the resampling step (CDF, ancestors, flag) */
+size_t fabhip_ais_smc_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner);
+/* fabhip_ais_run / fabhip_ais_phase with the resampling step in front of every transition they run.  Only entry j - 1 of the
+ * per-transition outputs is written by transition j's phase.  `partials` (sharded chains) with the mode on: FABHIP_ENOTSUP.
+ * Workspace: fabhip_ais_smc_workspace_bytes when the mode is on, fabhip_ais_workspace_bytes otherwise. */
+int fabhip_ais_run_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, fabhip_stream_t stream);
+int fabhip_ais_phase_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin,
+                         int32_t j_end, float* partials, fabhip_stream_t stream);
+
+/* The decision alone, for samplers that step their transitions themselves (the generic plug-in path): ancestors [B] (identity
+ * where nothing is resampled and beyond *n_ptr rows), resampled [1], log_w_common [1] (the value every log_w[:n0] takes when
+ * resampled[0] == 1) are required; ess [1] and log_w_pre [B] may be NULL.  n_ptr NULL: all B rows.  u: device, one double. */
+size_t fabhip_smc_workspace_bytes(int64_t B);
+int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
+                      int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
+                      size_t workspace_bytes, fabhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same with the RQ-spline flow (fabhip_spline_*) as base distribution

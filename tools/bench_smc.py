@@ -1,0 +1,77 @@
+"""Cost and effect of the SMC mode (AnnealedImportanceSampler.resample_threshold) on the headline workload: ManyWell-32, RealNVP
+10 x (16-320-320-32), M = 8, HMC L = 5, step-size tuning on, 1024 and 2048 chains.
+
+Timing: ms per `sample_and_log_weights` call (wall clock over CALLS calls, REPEATS repeats: median and the min .. max spread) for
+  off            the plain call as the benchmark runs it (prefetch of repeated calls on),
+  off/noprefetch the plain one-op call (the mode bypasses the prefetch: this is the like-for-like baseline of the next two),
+  tau=0          the decision runs before every transition and never fires,
+  tau=1.5        it fires every time (gather + copy-back move the whole point).
+log Z: error of the call's log_Z against the target's exact normaliser (AIS target p, tuning off, step 0.1) over SEEDS seeds for
+off and tau = 0.5, with the untrained seeded flow of the benchmark.  One JSON line."""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import fab_torch_amd as fa
+from bench import build_flow_state, _lib_srchash      # the bench's seeded headline flow
+
+DEV = "cuda"
+D, M, L = 32, 8, 5
+CALLS, REPEATS, SEEDS = int(os.environ.get("CALLS", 200)), int(os.environ.get("REPEATS", 5)), int(os.environ.get("SEEDS", 8))
+flow = build_flow_state(0).to(DEV).requires_grad_(False)
+target = fa.ManyWellEnergy(D)
+
+
+def sampler(tau, p_target=False, tune=True, eps=0.1):
+    hmc = fa.HamiltonianMonteCarlo(M, D, flow.log_prob, target.log_prob, alpha=2.0, p_target=p_target, epsilon=eps, L=L,
+                                   eval_mode=not tune).to(DEV)
+    return fa.AnnealedImportanceSampler(flow, target.log_prob, hmc, p_target, 2.0, M, resample_threshold=tau)
+
+
+def time_setting(B, tau, prefetch):
+    ais = sampler(tau)
+    ais.prefetch = prefetch
+    torch.manual_seed(1)
+    for _ in range(100):
+        ais.sample_and_log_weights(B)
+    ms = []
+    for _ in range(REPEATS):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(CALLS):
+            ais.sample_and_log_weights(B)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) / CALLS * 1e3)
+    ms.sort()
+    info = ais.get_logging_info()
+    return {"ms_median": ms[len(ms) // 2], "ms_min": ms[0], "ms_max": ms[-1], "n_resampled": info.get("n_resampled"),
+            "ess_ais": info["ess_ais"]}
+
+
+def log_z_errors(B, tau):
+    errs, n_res = [], 0
+    for seed in range(SEEDS):
+        ais = sampler(tau, p_target=True, tune=False)
+        torch.manual_seed(100 + seed)
+        ais.sample_and_log_weights(B)
+        info = ais.get_logging_info()
+        errs.append(info["log_Z"] - float(target.log_Z))
+        n_res += info.get("n_resampled", 0)
+    t = torch.tensor(errs, dtype=torch.float64)
+    return {"mean": float(t.mean()), "std": float(t.std()), "min": float(t.min()), "max": float(t.max()), "n_resampled": n_res,
+            "of_steps": SEEDS * M}
+
+
+out = {"config": f"ManyWell-{D}, RealNVP 10x(16-320-320-32), M={M}, HMC L={L}", "lib_srchash": _lib_srchash()[:12],
+       "calls": CALLS, "repeats": REPEATS}
+for B in (1024, 2048):
+    row = {"off": time_setting(B, None, True), "off_noprefetch": time_setting(B, None, False),
+           "tau_0": time_setting(B, 0.0, False), "tau_1.5": time_setting(B, 1.5, False)}
+    base = row["off_noprefetch"]["ms_median"]
+    row["us_per_transition_tau_0"] = (row["tau_0"]["ms_median"] - base) / M * 1e3
+    row["us_per_transition_tau_1.5"] = (row["tau_1.5"]["ms_median"] - base) / M * 1e3
+    out[f"B{B}"] = row
+out["log_Z_error_B1024"] = {"off": log_z_errors(1024, None), "tau_0.5": log_z_errors(1024, 0.5)}
+print(json.dumps(out))
