@@ -113,8 +113,9 @@ SYMBOLS = [
     "fabhip_flow_pack_train", "fabhip_flow_log_prob_tape_rows", "fabhip_train_step_workspace_bytes", "fabhip_buffer_train_step",
     "fabhip_buffer_add", "fabhip_buffer_sample_workspace_bytes", "fabhip_buffer_sample",
     "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
+    "fabhip_train_step_plan",
 ]
-ABI_VERSION = 217          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 218          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -181,6 +182,7 @@ def _declare(lib):
     lib.fabhip_spline_packed_floats.argtypes = [i32, i32, i32]
     lib.fabhip_spline_tape_layout.argtypes = [i32, i32, i32, i64, C.POINTER(i64)]
     lib.fabhip_flow_tape_layout.argtypes = [i32, i32, i32, i64, C.POINTER(i64)]
+    lib.fabhip_train_step_plan.argtypes = [i32, i32, i32, C.POINTER(i64)]
     lib.fabhip_flow_log_prob_tape.argtypes = [C.POINTER(Flow), vp, vp, vp, i64, vp, sz, vp]
     lib.fabhip_flow_param_grad.argtypes = [C.POINTER(FlowParams), C.POINTER(Flow), vp, sz, vp, i64, vp, vp]
     lib.fabhip_flow_sample_grad_tape.argtypes = [C.POINTER(Flow), vp, vp, vp, vp, i64, vp, sz, vp]

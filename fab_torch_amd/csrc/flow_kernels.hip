@@ -848,7 +848,7 @@ static int flow_pack_impl(const fabhip_flow_params* p, float* packed, int with_i
         }
         hipLaunchKernelGGL(k_affine_assemble, dim3(nl), dim3(f.D <= 32 ? 1024 : 256), smem, st, f, at, k0, packed, with_inverse == 1 ? 1 : 0);
         // training image + 8-chain tape tiles: the bias blocks only, with the base distribution in the same launch
-        const bool heads_only = with_inverse == 2 && f.o_r8 >= 0 && option(FABHIP_OPT_TAPE_TILES) != 16;
+        const bool heads_only = with_inverse == 2 && tape_on_r8_tiles(f);
         const int off_begin = heads_only ? f.o_b1 : 0;
         const int nblk = ceil_div(f.o_logS - off_begin, 256 * 4);
         hipLaunchKernelGGL(k_pack_layer, dim3(nblk, nl), dim3(256), 0, st, f, mt, k0, packed, off_begin,

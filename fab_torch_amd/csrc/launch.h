@@ -25,6 +25,9 @@ static inline FlowDims flow_dims_of(const fabhip_flow& fl) {
 }
 // developer switches (fabhip_set_option; flow_kernels.hip): one int load, initialised from the environment at load time
 int option(int key);
+// The training tape runs on the 8-chain stream tiles (flow_r8.h) where the flow has that image, unless FABHIP_OPT_TAPE_TILES asks
+// for the 16-chain kernel: the ONE predicate of the training pack, of the tape forward and of the train step's plan.
+static inline bool tape_on_r8_tiles(const FlowDims& f) { return f.o_r8 >= 0 && option(FABHIP_OPT_TAPE_TILES) != 16; }
 // generic HMC pieces with the row count on the device (generic_kernels.hip; used by the fused spline AIS call)
 int gen_hmc_begin(const fabhip_point* start, const fabhip_point* cur, long B, int dim, fabhip_anneal c, const float* noise_p,
                   const float* mass, float max_grad, void* workspace, const int* n_valid, hipStream_t st);

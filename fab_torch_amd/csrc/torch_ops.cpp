@@ -350,6 +350,13 @@ void adam_clip_step(Tensor theta, const Tensor& grad, Tensor m, Tensor v, double
         "adam_clip_step");
 }
 
+// {tile rows of the tape kernel, G, tail fused} of fabhip::buffer_train_step for this flow under the current options
+std::vector<int64_t> train_step_plan(int64_t dim, int64_t n_layers, int64_t width) {
+    std::vector<int64_t> out(3);
+    chk(fabhip_train_step_plan((int32_t)dim, (int32_t)n_layers, (int32_t)width, out.data()), "train_step_plan");
+    return out;
+}
+
 // One gradient step on one minibatch of the prioritised replay buffer (fab/train_with_prioritised_buffer.py:158-185) as ONE op:
 // training pack, log q with the tape (the minibatch read in place from the buffer through `rows`), loss weights + buffer.adjust,
 // parameter gradients, clipped Adam - nine launches, no host synchronisation, no autograd graph.  `pset`: the flow's registered
@@ -1399,6 +1406,7 @@ TORCH_LIBRARY(fabhip, m) {
     m.def("flow_grad_floats(int dim, int n_layers, int width) -> int", flow_grad_floats);
     m.def("flow_grad_layout(int dim, int n_layers, int width) -> int[]", flow_grad_layout);
     m.def("flow_tape_layout(int dim, int n_layers, int width, int B) -> int[]", flow_tape_layout);
+    m.def("train_step_plan(int dim, int n_layers, int width) -> int[]", train_step_plan);
     m.def("set_fast_mode(bool on) -> int", set_fast_mode);
     m.def("get_fast_mode() -> int", get_fast_mode);
     m.def("set_option(int key, int value) -> int", set_option);

@@ -590,7 +590,7 @@ static int log_prob_tape_impl(const fabhip_flow* flow, const float* x, const int
     if (tape_bytes < tape_floats(f, td) * sizeof(float)) return FABHIP_ENOSPC;
     // 8-chain stream tiles where the flow has that image (D <= 32, hidden width padded to 256 / 320): twice the workgroups of the
     // 16-chain kernel on the same batch - a 2048-row minibatch fills the chip
-    if (option(FABHIP_OPT_TAPE_TILES) != 16 && f.o_r8 >= 0)
+    if (tape_on_r8_tiles(f))
         return launch_log_prob_tape_r8(f, td, flow->packed, x, rows, log_q, grad_x, (float*)tape, (long)B, (hipStream_t)stream);
     FAB_DISPATCH_NTW(f, launch_log_prob_tape, f, td, flow->packed, x, log_q, grad_x, (float*)tape, (long)B, rows,
                      (hipStream_t)stream);

@@ -530,11 +530,35 @@ __global__ __launch_bounds__(1024) void k_buffer_minibatch(MinibatchK a) {
     for (long b = tid + 1024l * KEEP; b < a.B; b += 1024) a.coef[b] = a.coef[b] * a.neg_inv_B * poison;
 }
 
+// Which kernels one fabhip_buffer_train_step call runs for a flow: the tape forward on 8-chain tiles where the flow has that image
+// (tape_on_r8_tiles, launch.h: the predicate the pack and the tape entry point decide by), and the minibatch arithmetic in that
+// kernel's tail only with the option at 0 (8: the 8-chain tiles with k_buffer_minibatch as a launch of its own, A/B).  The
+// dispatcher takes `tail` from here and fabhip_train_step_plan reports this struct, so what the query reports is what runs.
+struct TrainStepPlan {
+    int tile_rows, G, tail;
+};
+
+static TrainStepPlan make_train_step_plan(const FlowDims& f) {
+    TrainStepPlan p;
+    p.tile_rows = tape_on_r8_tiles(f) ? R8 : ROWS;
+    p.G = f.Wp / 64;
+    p.tail = (tape_on_r8_tiles(f) && option(FABHIP_OPT_TAPE_TILES) == 0) ? 1 : 0;
+    return p;
+}
+
 }  // namespace fab
 
 using namespace fab;
 
 extern "C" {
+
+int fabhip_train_step_plan(int32_t dim, int32_t n_layers, int32_t width, int64_t* out3) {
+    if (!out3) return FABHIP_EINVAL;
+    FAB_TRY(check_flow_shape(dim, n_layers, width));
+    const TrainStepPlan p = make_train_step_plan(make_flow_dims(dim, n_layers, width));
+    out3[0] = p.tile_rows; out3[1] = p.G; out3[2] = p.tail;
+    return FABHIP_OK;
+}
 
 size_t fabhip_train_step_workspace_bytes(int32_t dim, int32_t n_layers, int32_t width, int64_t B, int64_t n_params) {
     const size_t tape = fabhip_flow_tape_bytes(dim, n_layers, width, B);
@@ -569,7 +593,7 @@ int fabhip_buffer_train_step(const fabhip_train_step_args* a, fabhip_stream_t st
     const TapeDims td = make_tape_dims(f, (long)a->B);
     char* adam_ws = (char*)a->workspace + tape_al;
     const size_t adam_bytes = a->workspace_bytes - tape_al;
-    const bool tail = f.o_r8 >= 0 && option(FABHIP_OPT_TAPE_TILES) == 0;       // (8: the 8-chain tiles without the fused tail, A/B)
+    const bool tail = make_train_step_plan(f).tail != 0;
     const int n_part = 2 * (int)(td.Bp / R8);
     float* partials = (float*)(adam_ws + ((fabhip_adam_workspace_bytes(a->n_params) + 255) & ~(size_t)255));
     if (tail) {

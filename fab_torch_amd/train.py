@@ -91,6 +91,10 @@ class PrioritisedBufferTrainer:
         self.history: List[Dict] = []
         self._fused = isinstance(optimizer, FlatAdam) and optimizer.native      # tape + flat-image kernels: RealNVP
         self._flat = isinstance(optimizer, FlatAdam)                            # fused clip + Adam for any flow
+        # the gradient norm the iteration logs is the last one that was COMPUTED: a minibatch skipped for its non-finite loss
+        # computes none, and the reference's variable lives across iterations (:172-198) - None until the first one exists
+        self._last_grad_norm = None
+        self._minibatch_record: List[Dict] = []                                 # see minibatch_stats()
 
     def step(self, i: int, batch_size: int, noise: Optional[Dict] = None) -> Dict:
         """One iteration of train_with_prioritised_buffer.py:138-198.  `noise` (optional, parity replays): the random
@@ -108,7 +112,9 @@ class PrioritisedBufferTrainer:
         mini_dataset = buf.sample_n_batches(batch_size=batch_size, n_batches=self.n_batches_buffer_sampling,
                                             gumbel=noise.get("gumbel"), perm=noise.get("perm"))
         self.last_indices = torch.cat([m[3] for m in mini_dataset])
-        loss = grad_norm = None
+        loss, grad_norm = None, self._last_grad_norm
+        # per minibatch, as device tensors (no reduction, no synchronisation here): loss, the norm variable, weights, log q
+        record = self._minibatch_record = []
         for (x, log_w, log_q_old, indices) in mini_dataset:
             self.optimizer.zero_grad()
             if self._fused:
@@ -129,9 +135,11 @@ class PrioritisedBufferTrainer:
                     # on-device finite-norm check of fabhip_adam_clip_step then skips (reference :172-181)
                     poison = torch.where(torch.isfinite(loss), 1.0, float("nan"))
                     flat = model.flow.param_grad_flat(tape, w_adjust * (-1.0 / x.shape[0]) * poison)
-                grad_norm = self.optimizer.step(max_grad_norm=self.max_gradient_norm, flat_grad=flat)
+                grad_norm = self._norm_unless_loss_skip(
+                    loss, self.optimizer.step(max_grad_norm=self.max_gradient_norm, flat_grad=flat), grad_norm)
                 if not self.w_adjust_in_buffer_after_update:
                     buf.adjust(log_w_adjust, log_q_x, indices)
+                record.append(dict(loss=loss, grad_norm=grad_norm, w_adjust_pre_clip=w_adjust_pre_clip, log_q_x=log_q_x))
                 continue
             log_q_x = model.flow.log_prob(x)
             log_w_adjust = (1 - self.alpha) * (log_q_x.detach() - log_q_old)
@@ -143,7 +151,8 @@ class PrioritisedBufferTrainer:
                 # FlatAdam on a non-RealNVP flow: autograd for the gradients, then ONE fused clip + Adam launch whose
                 # on-device finite-norm check skips the update (a non-finite loss poisons the gradient: reference :172-181)
                 (loss * torch.where(torch.isfinite(loss.detach()), 1.0, float("nan"))).backward()
-                grad_norm = self.optimizer.step(max_grad_norm=self.max_gradient_norm)
+                grad_norm = self._norm_unless_loss_skip(
+                    loss.detach(), self.optimizer.step(max_grad_norm=self.max_gradient_norm), grad_norm)
             elif torch.isfinite(loss):
                 loss.backward()
                 grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), self.max_gradient_norm)
@@ -155,6 +164,9 @@ class PrioritisedBufferTrainer:
                 print("nan loss in replay step")
             if not self.w_adjust_in_buffer_after_update:
                 buf.adjust(log_w_adjust, log_q_x.detach(), indices)
+            record.append(dict(loss=loss.detach(), grad_norm=grad_norm, w_adjust_pre_clip=w_adjust_pre_clip.detach(),
+                               log_q_x=log_q_x.detach()))
+        self._last_grad_norm = grad_norm
         info.update(loss=loss.item(), step=i, grad_norm=float(grad_norm) if grad_norm is not None else float("nan"),
                     sampled_log_w_std=torch.std(log_w).item(), sampled_log_w_mean=torch.mean(log_w).item(),
                     w_adjust_mean=torch.mean(w_adjust_pre_clip).item(), w_adjust_min=torch.min(w_adjust_pre_clip).item(),
@@ -167,6 +179,32 @@ class PrioritisedBufferTrainer:
         # NB: like the reference, this trainer never steps `optim_schedular` (it is only checkpointed, :59-68);
         # fab/train.py:110-111 is the loop that steps it.
         return info
+
+    @staticmethod
+    def _norm_unless_loss_skip(loss, new_norm, last_norm):
+        """FlatAdam paths (the finite-loss test runs on the device: poisoned coefficients give a NaN norm there): the norm of
+        this minibatch if its loss is finite, else the last computed one (NaN when none exists) - no host synchronisation."""
+        if last_norm is None:
+            last_norm = torch.full_like(new_norm, float("nan"))
+        return torch.where(torch.isfinite(loss), new_norm, torch.as_tensor(last_norm, device=new_norm.device))
+
+    def minibatch_stats(self) -> List[Dict]:
+        """Per minibatch of the last iteration (the reference logs only the last one, :189-198), as host floats on every path:
+        loss, grad_norm (the norm variable as it stood after the minibatch: the last computed one, NaN while none exists),
+        norm_computed (False for a minibatch skipped for its non-finite loss), mean / min / max of the weights before the clip,
+        mean log q.  On the one-op path these arrived with the iteration's one device-to-host read; on the step-by-step paths the
+        iteration kept device tensors and this call reduces and reads them."""
+        out = []
+        for s in self._minibatch_record:
+            if "w_adjust_pre_clip" in s:
+                w, gn, loss = s["w_adjust_pre_clip"], s["grad_norm"], float(s["loss"])
+                s = dict(loss=loss, w_adjust_mean=float(w.mean()), w_adjust_min=float(w.min()), w_adjust_max=float(w.max()),
+                         log_q_x_mean=float(s["log_q_x"].mean()), grad_norm=gn,
+                         norm_computed=loss == loss and abs(loss) != float("inf"))
+            s = dict(s)
+            s["grad_norm"] = float(s["grad_norm"]) if s["grad_norm"] is not None else float("nan")
+            out.append(s)
+        return out
 
     def _one_op_minibatch(self) -> bool:
         """The whole minibatch body as ONE op (fabhip::buffer_train_step): RealNVP + FlatAdam, the buffer on the flow's device and
@@ -194,7 +232,7 @@ class PrioritisedBufferTrainer:
         grp = opt.param_groups[0]
         clip = float(self.max_adjust_w_clip) if self.max_adjust_w_clip is not None else 0.0
         mx = 0.0 if self.max_gradient_norm == float("inf") else float(self.max_gradient_norm)
-        stats = None
+        stats, all_stats = None, []
         with torch.no_grad():
             theta = opt.theta.detach()
             for j, rows in enumerate(chunks):
@@ -202,6 +240,7 @@ class PrioritisedBufferTrainer:
                     handle, packed, D, K, W, j > 0, buf.buffer.x, rows.contiguous(), buf.buffer.log_q_old, True, float(self.alpha),
                     clip, buf.buffer.log_w, buf.buffer.log_q_old, theta, opt.m, opt.v, float(grp["lr"]),
                     float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), opt.steps, mx)
+                all_stats.append(stats[:6])
         flow._packed_key = None                                 # the parameters moved behind autograd's version counters (and the
         flow._packed_has_inverse = False                        # image holds the training tiles of the last-but-one parameters)
         opt.grad_norm.copy_(stats[5:6])
@@ -209,8 +248,22 @@ class PrioritisedBufferTrainer:
         # that the device-to-host read of the transition operator's statistics does not stall the queue in front of them
         info = model.get_iter_info()
         lw = torch.stack([torch.std(log_w_last), torch.mean(log_w_last)])
-        host = torch.cat([stats[:6], lw]).tolist()              # ONE device-to-host read for the iteration's logging values
-        info.update(loss=host[0], step=i, grad_norm=host[5], sampled_log_w_std=host[6], sampled_log_w_mean=host[7],
+        host = torch.cat(all_stats + [lw]).tolist()             # ONE device-to-host read for the iteration's logging values
+        # the logged gradient norm is the last one that was computed: the op reports NaN in [5] for a minibatch it skipped for its
+        # non-finite loss (no norm exists for it, :172-173), a finite loss reports the norm it found, finite or not (:174-179)
+        grad_norm = self._last_grad_norm
+        self._minibatch_record = []
+        for j in range(nb):
+            s = host[6 * j: 6 * j + 6]
+            stepped_loss = s[0] == s[0] and abs(s[0]) != float("inf")
+            if stepped_loss:
+                grad_norm = s[5]
+            self._minibatch_record.append(dict(loss=s[0], w_adjust_mean=s[1], w_adjust_min=s[2], w_adjust_max=s[3],
+                                                  log_q_x_mean=s[4], grad_norm=grad_norm, norm_computed=stepped_loss))
+        self._last_grad_norm = grad_norm
+        host, tail = host[6 * (nb - 1): 6 * nb], host[6 * nb:]
+        info.update(loss=host[0], step=i, grad_norm=float(grad_norm) if grad_norm is not None else float("nan"),
+                    sampled_log_w_std=tail[0], sampled_log_w_mean=tail[1],
                     w_adjust_mean=host[1], w_adjust_min=host[2], w_adjust_max=host[3], log_q_x_mean=host[4])
         return info
 

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 217
+#define FABHIP_ABI_VERSION 218
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -322,7 +322,10 @@ int fabhip_adam_clip_step(float* theta, const float* grad, float* m, float* v, i
  *   grads = sum_b coef_b d log q(x_b) / d theta (fabhip_flow_param_grad), then fabhip_adam_clip_step on (theta, m, v).
  * `params` point INTO theta (the flat layout of fabhip_flow_grad_layout: FlatAdam).  log_q_old: [B] (log_q_old_rows = 0) or the
  * buffer's log_q_old, read at rows[b] (= 1).  stats[8] (device): loss, mean / min / max of exp(log_w_adjust) before the clip,
- * mean(log_q), gradient norm - the reference's logging keys (:188-196).  struct_bytes = sizeof(fabhip_train_step_args). */
+ * mean(log_q), gradient norm - the reference's logging keys (:188-196); the norm is NaN for a minibatch skipped for its non-finite
+ * loss (the reference computes none there, :172-173: the caller keeps the last one it saw, as PrioritisedBufferTrainer does).
+ * stats[5] alone therefore does not tell "loss skipped" from "finite loss whose gradient norm is NaN" (:175-179, also no update):
+ * a caller that needs the difference tests stats[0] for finiteness first.  struct_bytes = sizeof(fabhip_train_step_args). */
 typedef struct {
     size_t struct_bytes;
     const fabhip_flow_params* params;
@@ -354,6 +357,10 @@ int fabhip_buffer_sample(const float* log_w, const float* u_gumbel, const float*
                          void* workspace, size_t workspace_bytes, fabhip_stream_t stream);
 size_t fabhip_train_step_workspace_bytes(int32_t dim, int32_t n_layers, int32_t width, int64_t B, int64_t n_params);
 int fabhip_buffer_train_step(const fabhip_train_step_args* args, fabhip_stream_t stream);
+/* What fabhip_buffer_train_step runs for this flow under the current FABHIP_OPT_TAPE_TILES (host-only, read-only; the dispatcher
+ * takes its decision from the same function): out3 = {rows per workgroup of the tape kernel (8 or 16), hidden column groups
+ * G = padded width / 64, 1 if the minibatch arithmetic runs in the tape kernel's tail / 0 if k_buffer_minibatch is launched}. */
+int fabhip_train_step_plan(int32_t dim, int32_t n_layers, int32_t width, int64_t* out3);
 
 /* ------------------------------------------------------------------------------------------
  * Targets (fab/target_distributions/many_well.py:81-90, double_well.py:44-58, gmm.py:57-66)

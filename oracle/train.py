@@ -14,10 +14,10 @@ import torch
 
 
 class Buffer:
-    def __init__(self, dim, max_length, min_sample_length):
-        self.x = torch.zeros(max_length, dim)
-        self.log_w = torch.zeros(max_length)
-        self.log_q_old = torch.zeros(max_length)
+    def __init__(self, dim, max_length, min_sample_length, dtype=torch.float32):
+        self.x = torch.zeros(max_length, dim, dtype=dtype)
+        self.log_w = torch.zeros(max_length, dtype=dtype)
+        self.log_q_old = torch.zeros(max_length, dtype=dtype)
         self.max_length, self.min_sample_length = max_length, min_sample_length
         self.current_index, self.is_full, self.can_sample = 0, False, False
 
@@ -47,14 +47,17 @@ class Buffer:
 
 
 def train_iteration(ais, flow_log_prob, params, optimizer, buffer: Buffer, alpha, batch_size, n_batches, noise,
-                    max_gradient_norm=5.0, w_adjust_max_clip=10.0):
+                    max_gradient_norm=5.0, w_adjust_max_clip=10.0, grad_norm=None):
     """One iteration of train_with_prioritised_buffer.py:138-198.  `ais`: oracle AIS; `noise` = dict(eps0, noise_p,
-    noise_e, gumbel, perm).  Returns the logged scalars + the sampled indices."""
+    noise_e, gumbel, perm).  Returns the logged scalars + the sampled indices + `minibatches`: per minibatch (the reference logs
+    only the last one) loss, grad_norm as the reference's variable stands after it, mean / min / max of the weights before the
+    clip, the number of clipped rows, mean log q, whether the optimiser stepped, and the log_w_adjust vector itself.  `grad_norm`: the reference's variable as the
+    previous iteration left it (it lives across the loop: a minibatch skipped for its non-finite loss computes none, :172-181)."""
     optimizer.zero_grad()
     pt, log_w_ais, info = ais.sample_and_log_weights(noise["eps0"], noise["noise_p"], noise["noise_e"])
     buffer.add(pt.x.detach(), log_w_ais.detach(), pt.log_q.detach())
     x, log_w, log_q_old, indices = buffer.sample(batch_size * n_batches, noise["gumbel"], noise["perm"])
-    loss = grad_norm = None
+    loss, minibatches = None, []
     for xb, lwb, lqb, ib in zip(torch.chunk(x, n_batches), torch.chunk(log_w, n_batches),
                                 torch.chunk(log_q_old, n_batches), torch.chunk(indices, n_batches)):
         optimizer.zero_grad()
@@ -63,13 +66,21 @@ def train_iteration(ais, flow_log_prob, params, optimizer, buffer: Buffer, alpha
         w_pre = torch.exp(log_w_adjust)
         w_adjust = torch.clip(w_pre, max=w_adjust_max_clip) if w_adjust_max_clip is not None else w_pre
         loss = -torch.mean(w_adjust * log_q_x)
+        stepped = False
         if not torch.isnan(loss) and not torch.isinf(loss):
             loss.backward()
             grad_norm = torch.nn.utils.clip_grad_norm_(params, max_gradient_norm)
             if torch.isfinite(grad_norm):
                 optimizer.step()
+                stepped = True
         with torch.no_grad():
             buffer.adjust(log_w_adjust, log_q_x.detach(), ib)
-    return dict(loss=float(loss.detach()), grad_norm=float(grad_norm), indices=indices, ess_ais=info.ess_ais,
+            n_clipped = int((w_pre > w_adjust_max_clip).sum()) if w_adjust_max_clip is not None else 0
+            minibatches.append(dict(loss=float(loss.detach()), grad_norm=float(grad_norm) if grad_norm is not None else float("nan"),
+                                    w_adjust_mean=float(w_pre.mean()), w_adjust_min=float(w_pre.min()),
+                                    w_adjust_max=float(w_pre.max()), n_clipped=n_clipped, log_q_x_mean=float(log_q_x.mean()),
+                                    stepped=int(stepped), log_w_adjust=log_w_adjust.detach().clone()))
+    return dict(loss=float(loss.detach()), grad_norm=float(grad_norm) if grad_norm is not None else float("nan"),
+                grad_norm_carry=grad_norm, minibatches=minibatches, indices=indices, ess_ais=info.ess_ais,
                 ess_base=info.ess_base, log_Z=info.log_Z, w_adjust_mean=float(w_pre.mean()),
                 log_q_x_mean=float(log_q_x.mean()), sampled_log_w_mean=float(lwb.mean()))

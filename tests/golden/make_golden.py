@@ -603,11 +603,13 @@ def g11_gmm_eval():
         ess_over_p=effective_sample_size_over_p(0.5 * log_w))
 
 
-def g12_trainer_traces():
-    """R14: the reference's PrioritisedBufferTrainer.run (fab/train_with_prioritised_buffer.py:106-255) driven for 5
-    iterations on ManyWell-6 with the oracle flow as the trainable distribution, seeds {0, 1, 2}; every random draw
-    (flow base noise, HMC momenta / Exp(1), the buffer's Gumbel noise and permutation) is captured together with the
-    per-iteration loss, grad_norm, sampled indices and the buffer's log_w / log_q_old after the on-the-fly adjust."""
+def reference_trainer_trace(nf, D, K, nodes, M, L, B, alpha, n_iter, n_batches, buf_len, buf_min, lr, eps_init, rng_seed):
+    """The reference's PrioritisedBufferTrainer.run (fab/train_with_prioritised_buffer.py:106-255) driven for n_iter iterations on
+    ManyWell-D with the oracle flow `nf` as the trainable distribution (max_gradient_norm 5, w_adjust_max_clip 10); every random
+    draw (flow base noise, HMC momenta / Exp(1), the buffer's Gumbel noise and permutation) is captured together with the
+    per-iteration loss, grad_norm, sampled indices and the buffer's log_w / log_q_old after the on-the-fly adjust.  Returns
+    (trace, start-of-iteration states, extras: per-minibatch scalars, step sizes and - in memory - the parameters at every
+    iteration start and at the end)."""
     import torch.nn as nn
     import fab.utils.prioritised_replay_buffer as prb
     from fab.utils.prioritised_replay_buffer import PrioritisedReplayBuffer
@@ -638,111 +640,268 @@ def g12_trainer_traces():
         def event_shape(self):
             return self.nf.q0.shape
 
+    flow = OracleTrainable(nf)
+    target = ManyWellEnergy(dim=D, use_gpu=False)
+    hmc = HamiltonianMonteCarlo(n_ais_intermediate_distributions=M, dim=D, base_log_prob=flow.log_prob,
+                                target_log_prob=target.log_prob, alpha=alpha, p_target=False, epsilon=eps_init,
+                                n_outer=1, L=L)
+    model = FABModel(flow=flow, target_distribution=target, n_intermediate_distributions=M, alpha=alpha,
+                     transition_operator=hmc)
+    out = dict(D=D, K=K, nodes=nodes, M=M, L=L, B=B, alpha=alpha, n_iter=n_iter, n_batches=n_batches,
+               buf_len=buf_len, buf_min=buf_min, lr=lr, max_gradient_norm=5.0, w_adjust_max_clip=10.0,
+               in_epsilons=hmc.epsilons.clone(), in_common_epsilon=hmc.common_epsilon.clone())
+    out.update({k: v.detach().clone() for k, v in flow_state(nf).items()})     # the INITIAL parameters
+    ais = model.annealed_importance_sampler
+    calls = []
+    orig_call = ais.sample_and_log_weights
+
+    starts = []                                              # state at the START of every trainer iteration (teacher forcing)
+    snapshots, minibatches = [], []                          # parameters at every iteration start; per-minibatch scalars
+    holder = {}
+
+    def recording_call(batch_size, logging=True):
+        if "opt" in holder:                                  # a trainer iteration begins with this call
+            snapshots.append([p_.detach().clone() for p_ in nf.parameters()])
+            st = holder["opt"].state_dict()["state"]
+            starts.append(dict(params={k: v.detach().clone() for k, v in nf.state_dict().items()},
+                               adam={i: (d["exp_avg"].clone(), d["exp_avg_sq"].clone(), float(d["step"]))
+                                     for i, d in st.items()},
+                               eps=hmc.epsilons.clone(), ceps=hmc.common_epsilon.clone(),
+                               buf_x=buffer.buffer.x.clone(), buf_index=int(buffer.current_index),
+                               buf_full=int(buffer.is_full)))
+        with Capture() as cap:
+            res = orig_call(batch_size, logging)
+        calls.append(dict(eps0=cap.randn[0], noise_p=torch.stack(cap.randn_like)[:, None],
+                          noise_e=torch.stack(cap.expo)[:, None], x=res[0].x.clone(), log_w=res[1].clone(),
+                          log_q=res[0].log_q.clone()))
+        return res
+    ais.sample_and_log_weights = recording_call
+    gumbel, perms = [], []
+    o_ts, o_rp = TransformedDistribution.sample, torch.randperm
+
+    def ts(self_, shape=torch.Size()):
+        z = o_ts(self_, shape); gumbel.append(z.clone()); return z
+
+    def rp(*a, **k):
+        p_ = o_rp(*a, **k); perms.append(p_.clone()); return p_
+    torch.manual_seed(rng_seed)
+
+    def initial_sampler():
+        pt, lw = ais.sample_and_log_weights(B, logging=False)
+        return pt.x, lw, pt.log_q
+    buffer = PrioritisedReplayBuffer(dim=D, max_length=buf_len, min_sample_length=buf_min,
+                                     initial_sampler=initial_sampler)
+    n_init_calls = len(calls)
+    opt = torch.optim.Adam(flow.parameters(), lr=lr)
+    holder["opt"] = opt
+    logger = ListLogger()
+    trainer = PrioritisedBufferTrainer(model=model, optimizer=opt, buffer=buffer, alpha=alpha,
+                                       n_batches_buffer_sampling=n_batches, logger=logger,
+                                       max_gradient_norm=5.0, w_adjust_max_clip=10.0)
+    snaps = []
+    o_write = logger.write
+
+    def write(info):
+        o_write(info)
+        snaps.append((buffer.buffer.log_w.clone(), buffer.buffer.log_q_old.clone()))
+    logger.write = write
+    o_sample = buffer.sample
+    idx_log = []
+
+    def sample(batch_size):
+        r = o_sample(batch_size); idx_log.append(r[3].clone()); return r
+    buffer.sample = sample
+    # per minibatch (the trainer logs only the last one): what its loop computed, recomputed by the same torch expressions from the
+    # tensors it hands to buffer.adjust (:164-171, bit-identical), and its `grad_norm` variable as it stands after the minibatch
+    o_clip, o_step, o_adjust = torch.nn.utils.clip_grad_norm_, opt.step, buffer.adjust
+    mb_state = dict(norm=float("nan"), stepped=0)
+
+    def clip_hook(*a, **k):
+        r = o_clip(*a, **k); mb_state["norm"] = float(r); return r
+
+    def step_hook(*a, **k):
+        mb_state["stepped"] = 1; return o_step(*a, **k)
+
+    def adjust_hook(log_w_adjust, log_q_x, indices):
+        w_pre = torch.exp(log_w_adjust)
+        w = torch.clip(w_pre, max=10.0)
+        minibatches.append(dict(loss=float(-torch.mean(w * log_q_x)), grad_norm=mb_state["norm"], w_adjust_mean=float(w_pre.mean()),
+                                w_adjust_min=float(w_pre.min()), w_adjust_max=float(w_pre.max()), n_clipped=int((w_pre > 10.0).sum()),
+                                log_q_x_mean=float(log_q_x.mean()), stepped=mb_state["stepped"]))
+        mb_state["stepped"] = 0
+        return o_adjust(log_w_adjust, log_q_x, indices)
+    opt.step, buffer.adjust = step_hook, adjust_hook
+    TransformedDistribution.sample, torch.randperm, torch.nn.utils.clip_grad_norm_ = ts, rp, clip_hook
+    try:
+        trainer.run(n_iterations=n_iter, batch_size=B, save=False)
+    finally:
+        TransformedDistribution.sample, torch.randperm, torch.nn.utils.clip_grad_norm_ = o_ts, o_rp, o_clip
+    snapshots.append([p_.detach().clone() for p_ in nf.parameters()])
+    assert len(minibatches) == n_iter * n_batches and len(snapshots) == n_iter + 1
+    assert len(calls) == n_init_calls + n_iter and len(gumbel) == n_iter == len(perms) == len(idx_log)
+    out["n_init_calls"] = n_init_calls
+    for c, d in enumerate(calls):
+        for k, v in d.items():
+            out[f"call{c}_{k}"] = v
+    hist = logger.history
+    for it in range(n_iter):
+        out[f"it{it}_gumbel"], out[f"it{it}_perm"], out[f"it{it}_indices"] = gumbel[it], perms[it], idx_log[it]
+        out[f"it{it}_buf_log_w"], out[f"it{it}_buf_log_q_old"] = snaps[it]
+        for key in ("loss", "grad_norm", "ess_ais", "ess_base", "log_Z", "w_adjust_mean", "log_q_x_mean",
+                    "sampled_log_w_mean"):
+            out[f"it{it}_{key}"] = hist[key][it]
+    out["out_epsilons"], out["out_common_epsilon"] = hmc.epsilons, hmc.common_epsilon
+    out.update({"final." + k: v for k, v in nf.state_dict().items()})
+    assert len(starts) == n_iter
+    tf = dict(n_iter=n_iter)
+    for it, st in enumerate(starts):
+        tf.update({f"it{it}_param.{k}": v for k, v in st["params"].items()})
+        for i, (m_, v_, step) in st["adam"].items():
+            tf[f"it{it}_adam_m.{i}"], tf[f"it{it}_adam_v.{i}"], tf[f"it{it}_adam_step.{i}"] = m_, v_, step
+        tf[f"it{it}_eps"], tf[f"it{it}_ceps"] = st["eps"], st["ceps"]
+        tf[f"it{it}_buf_x"], tf[f"it{it}_buf_index"], tf[f"it{it}_buf_full"] = st["buf_x"], st["buf_index"], st["buf_full"]
+    tf["n_adam"] = len(starts[-1]["adam"])
+    extra = dict(snapshots=snapshots)                    # (in memory only: the caller stores probes of them, helpers.param_probes)
+    for it in range(n_iter):
+        extra[f"it{it}_eps"], extra[f"it{it}_ceps"] = starts[it]["eps"], starts[it]["ceps"]
+        for j in range(n_batches):
+            for key, v in minibatches[it * n_batches + j].items():
+                extra[f"it{it}_mb{j}_{key}"] = v
+        last = minibatches[it * n_batches + n_batches - 1]             # the hooks see what the trainer logged
+        for key in ("loss", "w_adjust_max", "grad_norm"):
+            assert hist[key][it] == last[key] or (np.isnan(hist[key][it]) and np.isnan(last[key])), (it, key)
+    return out, tf, extra
+
+
+def g12_trainer_traces():
+    """R14: the reference trainer for 5 iterations on ManyWell-6 (RealNVP 3 x W = 30, B = 64), seeds {0, 1, 2}: the trace and, in a
+    second file, the start-of-iteration states (parameters, Adam moments, step sizes, buffer positions) the GPU test restarts every
+    iteration from."""
     D, K, nodes, M, L, B, alpha, n_iter, n_batches = 6, 3, 5, 4, 5, 64, 2.0, 5, 2
-    buf_len, buf_min = 8 * B, 2 * B
     for seed in (0, 1, 2):
         nf = make_flow(D, K, nodes, seed=60 + seed)
-        flow = OracleTrainable(nf)
-        target = ManyWellEnergy(dim=D, use_gpu=False)
-        hmc = HamiltonianMonteCarlo(n_ais_intermediate_distributions=M, dim=D, base_log_prob=flow.log_prob,
-                                    target_log_prob=target.log_prob, alpha=alpha, p_target=False, epsilon=0.2,
-                                    n_outer=1, L=L)
-        model = FABModel(flow=flow, target_distribution=target, n_intermediate_distributions=M, alpha=alpha,
-                         transition_operator=hmc)
-        out = dict(D=D, K=K, nodes=nodes, M=M, L=L, B=B, alpha=alpha, n_iter=n_iter, n_batches=n_batches,
-                   buf_len=buf_len, buf_min=buf_min, lr=1e-3, max_gradient_norm=5.0, w_adjust_max_clip=10.0,
-                   in_epsilons=hmc.epsilons.clone(), in_common_epsilon=hmc.common_epsilon.clone())
-        out.update({k: v.detach().clone() for k, v in flow_state(nf).items()})     # the INITIAL parameters
-        ais = model.annealed_importance_sampler
-        calls = []
-        orig_call = ais.sample_and_log_weights
-
-        starts = []                                              # state at the START of every trainer iteration (teacher forcing)
-        holder = {}
-
-        def recording_call(batch_size, logging=True):
-            if "opt" in holder:                                  # a trainer iteration begins with this call
-                st = holder["opt"].state_dict()["state"]
-                starts.append(dict(params={k: v.detach().clone() for k, v in nf.state_dict().items()},
-                                   adam={i: (d["exp_avg"].clone(), d["exp_avg_sq"].clone(), float(d["step"]))
-                                         for i, d in st.items()},
-                                   eps=hmc.epsilons.clone(), ceps=hmc.common_epsilon.clone(),
-                                   buf_x=buffer.buffer.x.clone(), buf_index=int(buffer.current_index),
-                                   buf_full=int(buffer.is_full)))
-            with Capture() as cap:
-                res = orig_call(batch_size, logging)
-            calls.append(dict(eps0=cap.randn[0], noise_p=torch.stack(cap.randn_like)[:, None],
-                              noise_e=torch.stack(cap.expo)[:, None], x=res[0].x.clone(), log_w=res[1].clone(),
-                              log_q=res[0].log_q.clone()))
-            return res
-        ais.sample_and_log_weights = recording_call
-        gumbel, perms = [], []
-        o_ts, o_rp = TransformedDistribution.sample, torch.randperm
-
-        def ts(self_, shape=torch.Size()):
-            z = o_ts(self_, shape); gumbel.append(z.clone()); return z
-
-        def rp(*a, **k):
-            p_ = o_rp(*a, **k); perms.append(p_.clone()); return p_
-        torch.manual_seed(1000 + seed)
-
-        def initial_sampler():
-            pt, lw = ais.sample_and_log_weights(B, logging=False)
-            return pt.x, lw, pt.log_q
-        buffer = PrioritisedReplayBuffer(dim=D, max_length=buf_len, min_sample_length=buf_min,
-                                         initial_sampler=initial_sampler)
-        n_init_calls = len(calls)
-        opt = torch.optim.Adam(flow.parameters(), lr=1e-3)
-        holder["opt"] = opt
-        logger = ListLogger()
-        trainer = PrioritisedBufferTrainer(model=model, optimizer=opt, buffer=buffer, alpha=alpha,
-                                           n_batches_buffer_sampling=n_batches, logger=logger,
-                                           max_gradient_norm=5.0, w_adjust_max_clip=10.0)
-        snaps = []
-        o_write = logger.write
-
-        def write(info):
-            o_write(info)
-            snaps.append((buffer.buffer.log_w.clone(), buffer.buffer.log_q_old.clone()))
-        logger.write = write
-        o_sample = buffer.sample
-        idx_log = []
-
-        def sample(batch_size):
-            r = o_sample(batch_size); idx_log.append(r[3].clone()); return r
-        buffer.sample = sample
-        TransformedDistribution.sample, torch.randperm = ts, rp
-        try:
-            trainer.run(n_iterations=n_iter, batch_size=B, save=False)
-        finally:
-            TransformedDistribution.sample, torch.randperm = o_ts, o_rp
-        assert len(calls) == n_init_calls + n_iter and len(gumbel) == n_iter == len(perms) == len(idx_log)
-        out["n_init_calls"] = n_init_calls
-        for c, d in enumerate(calls):
-            for k, v in d.items():
-                out[f"call{c}_{k}"] = v
-        hist = logger.history
-        for it in range(n_iter):
-            out[f"it{it}_gumbel"], out[f"it{it}_perm"], out[f"it{it}_indices"] = gumbel[it], perms[it], idx_log[it]
-            out[f"it{it}_buf_log_w"], out[f"it{it}_buf_log_q_old"] = snaps[it]
-            for key in ("loss", "grad_norm", "ess_ais", "ess_base", "log_Z", "w_adjust_mean", "log_q_x_mean",
-                        "sampled_log_w_mean"):
-                out[f"it{it}_{key}"] = hist[key][it]
-        out["out_epsilons"], out["out_common_epsilon"] = hmc.epsilons, hmc.common_epsilon
-        out.update({"final." + k: v for k, v in nf.state_dict().items()})
+        out, tf, _ = reference_trainer_trace(nf, D, K, nodes, M, L, B, alpha, n_iter, n_batches, 8 * B, 2 * B, 1e-3, 0.2, 1000 + seed)
         npz(f"g12_trainer_seed{seed}.npz", **out)
-        # start-of-iteration states (parameters, Adam moments, step sizes, buffer positions) in a second file: the GPU test
-        # restarts every iteration from the REFERENCE's state and compares one iteration at the north-star 1e-4
-        assert len(starts) == n_iter
-        tf = dict(n_iter=n_iter)
-        for it, st in enumerate(starts):
-            tf.update({f"it{it}_param.{k}": v for k, v in st["params"].items()})
-            for i, (m_, v_, step) in st["adam"].items():
-                tf[f"it{it}_adam_m.{i}"], tf[f"it{it}_adam_v.{i}"], tf[f"it{it}_adam_step.{i}"] = m_, v_, step
-            tf[f"it{it}_eps"], tf[f"it{it}_ceps"] = st["eps"], st["ceps"]
-            tf[f"it{it}_buf_x"], tf[f"it{it}_buf_index"], tf[f"it{it}_buf_full"] = st["buf_x"], st["buf_index"], st["buf_full"]
-        tf["n_adam"] = len(starts[-1]["adam"])
         npz(f"g12_trainer_seed{seed}_starts.npz", **tf)
+
+
+G18_TRACES = {   # name: (D, K, nodes, last-layer std, HMC epsilon, lr, flow seed)
+    "g18_trainer_w320_mild": (32, 10, 10, 0.01, 0.05, 1e-4, 180),
+    "g18_trainer_w320_clip": (32, 10, 10, 0.01, 0.05, 1e-3, 180),
+    "g18_trainer_w256_mild": (6, 3, 40, 0.01, 0.05, 1e-4, 180),
+}
+
+
+def _g18_trace(D, K, nodes, std, eps, lr, flow_seed, rng_seed):
+    """One g18 trace as a dict of arrays (everything but the parameter probes) and the parameter snapshots they are taken from."""
+    from helpers import seeded_oracle_flow
+    M, L, B, alpha, n_iter, n_batches = 4, 5, 64, 2.0, 3, 2
+    nf = seeded_oracle_flow(D, K, nodes, flow_seed, std)
+    probe = torch.stack([nf.flows[0].flows[1].param_map.net[2].weight[0, :8].detach().clone(),
+                         nf.flows[-2].flows[1].param_map.net[4].weight[1, :8].detach().clone()])
+    out, _, extra = reference_trainer_trace(nf, D, K, nodes, M, L, B, alpha, n_iter, n_batches, 8 * B, 2 * B, lr, eps, rng_seed)
+    snapshots = extra.pop("snapshots")
+    out = {k: v for k, v in out.items() if not (k.startswith("flow.") or k.startswith("final."))}
+    out.update(extra, flow_seed=flow_seed, flow_std=std, flow_probe=probe, eps_init=eps)
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()}, snapshots
+
+
+def g18_rough_search(n_seeds=20, save=True):
+    """`g18_trainer_w320_rough`: the reference trainer at D = 32, 10 layers, W = 320 in g12's own rough settings (last-layer std
+    0.05, HMC epsilon 0.2, lr 1e-3), where it drops chains, skips minibatches for a non-finite loss ("nan loss in replay step"),
+    kills buffer rows and logs a gradient norm an earlier minibatch computed.  A trace is only usable as a fixture if its
+    non-finite events are non-finite by construction and not by where float32 overflows.  Selection rule, applied to the draws'
+    seeds 1000 ... 1000 + n_seeds - 1 (at most 20) in order, first qualifying seed wins: the reference skips at least one
+    minibatch, and in a float64 replay of the trace by the oracle (`helpers.g18_oracle_replay(dtype=float64)`: the same captured
+    draws, nothing of the package involved)
+      (a) every buffer row that is non-finite in the trace after an iteration is non-finite in the replay as well,
+      (b) every minibatch the reference skipped has a non-finite loss in the replay,
+      (c) every finite log_w_adjust of the replay is below 60 in magnitude.
+    OUTCOME (20 seeds tried, 1000 ... 1019): NONE qualifies, so the fixture does not exist and the skip semantics are carried by
+    the non-finite cases and the skipped-minibatch trainer test of tests/test_gpu_train_step.py.  Why: the float64 run does not
+    drop the chains the float32 run dropped, so it leaves the trace at once - for 15 seeds (1000, the one of the mild / clip
+    traces, among them) the draws captured per surviving chain no longer fit the replay's chain counts and it cannot be run to
+    the end; for the other 5 (1003, 1007, 1012, 1015, 1018) it runs, samples other rows and reaches |log_w_adjust| of 9e18 and
+    more (c), on 1007 and 1012 with finite losses where the reference skipped (b), on 1012 with finite rows where it killed (a).
+    13 of the 20 traces skip at least one minibatch.  Returns the qualifying seed or None."""
+    from helpers import g18_oracle_replay, param_probes
+    import contextlib
+    import io
+    D, K, nodes, std, eps, lr, flow_seed = 32, 10, 10, 0.05, 0.2, 1e-3, 180
+    assert n_seeds <= 20
+    for rng_seed in range(1000, 1000 + n_seeds):
+        try:
+            with contextlib.redirect_stderr(io.StringIO()), contextlib.redirect_stdout(io.StringIO()):
+                out, snapshots = _g18_trace(D, K, nodes, std, eps, lr, flow_seed, rng_seed)
+        except Exception as e:                                                       # noqa: BLE001 (the reference's own failure)
+            print(f"rough seed {rng_seed}: the reference's run raised {type(e).__name__}")
+            continue
+        n_iter, n_batches = int(out["n_iter"]), int(out["n_batches"])
+        skipped = [(i, j) for i in range(n_iter) for j in range(n_batches) if not int(out[f"it{i}_mb{j}_stepped"])]
+        try:
+            r = g18_oracle_replay(out, dtype=torch.float64)
+        except RuntimeError as e:                    # the draws captured per surviving chain do not fit the replay's chains
+            print(f"rough seed {rng_seed}: skipped {skipped}; the float64 replay cannot follow the trace ({str(e)[:70]})")
+            continue
+        rule_a = all(not np.isfinite(r["outs"][i]["buf_log_w"].numpy()[~np.isfinite(out[f"it{i}_buf_log_w"])]).any()
+                     for i in range(n_iter))
+        rule_b = all(not np.isfinite(r["outs"][i]["minibatches"][j]["loss"]) for i, j in skipped)
+        adj = torch.cat([m["log_w_adjust"] for o in r["outs"] for m in o["minibatches"]])
+        adj_max = float(adj[torch.isfinite(adj)].abs().max())
+        print(f"rough seed {rng_seed}: skipped {skipped}; float64 replay: (a) {rule_a} (b) {rule_b} (c) max |adj| = {adj_max:.3g}")
+        if skipped and rule_a and rule_b and adj_max < 60.0:
+            if save:
+                ref = [param_probes(s_, 18) for s_ in snapshots]
+                out["probe_seed"], out["rng_seed"] = np.asarray(18), np.asarray(rng_seed)
+                for it in range(n_iter):
+                    out[f"it{it}_param_probe"] = ref[it]
+                out["final_param_probe"] = ref[n_iter]
+                npz("g18_trainer_w320_rough.npz", **out)
+            return rng_seed
+    print(f"rough: none of {n_seeds} seeds qualifies; g18_trainer_w320_rough is not written")
+    return None
+
+
+def g18_trainer_traces_wide(only=None):
+    """The reference trainer at the widths whose tape kernel carries the minibatch arithmetic in its tail (hidden width padded to
+    320: the benchmarked D = 32, 10 layers; padded to 256: D = 6, W = 240): ManyWell-D, M = 4, L = 5, B = 64, 3 iterations x 2
+    minibatches, buffer 512 / 128.  `mild`: the weight clip never acts; `clip`: lr 1e-3, the clip (10) acts.  No parameters are
+    stored: the flow is `helpers.seeded_oracle_flow(seed, std)` (+ a weight probe, as g14), and per iteration start / at the end
+    a probe of every parameter tensor (`helpers.param_probes`: 16 entries at seeded positions, sum, squared norm); per MINIBATCH
+    loss, grad_norm as the reference's variable holds it, mean / min / max of the pre-clip weights, clipped rows, mean log q,
+    whether the optimiser stepped.  The start-of-iteration states of the teacher-forced GPU test come from oracle/train.py, which
+    tests/test_oracle_golden.py pins to this trace first.
+    `g18_trainer_w320_rough` (skipped minibatches, killed rows) exists only if `g18_rough_search` finds a seed: see there."""
+    from helpers import param_probes, g18_oracle_replay
+    n_iter = 3
+    for name, (D, K, nodes, std, eps, lr, seed) in G18_TRACES.items():
+        if only and name not in only:
+            continue
+        out, snapshots = _g18_trace(D, K, nodes, std, eps, lr, seed, 1000)
+        # the probe positions: a float64 replay of the trace by the oracle (free-running, nothing of the package involved) must meet
+        # the free-running GPU test's parameter criterion on them (2e-5 + 1e-4 x the largest probed entry, per tensor), or the
+        # positions' seed moves on.  Only the mild traces are replayed free-running.
+        r64 = g18_oracle_replay(out, dtype=torch.float64) if name.endswith("_mild") else None
+        for probe_seed in range(18, 38):
+            ref = [param_probes(s_, probe_seed) for s_ in snapshots]
+            if r64 is None:
+                break
+            names = [n for n, _ in r64["nf"].named_parameters()]
+            worst_ratio = 0.0
+            for st, b in zip(r64["starts"] + [r64["final"]], ref):
+                a = param_probes([st["params"][n] for n in names], probe_seed)
+                tol = 2e-5 + 1e-4 * np.abs(b[:, :-2]).max(axis=1, keepdims=True)
+                worst_ratio = max(worst_ratio, float((np.abs(a[:, :-2] - b[:, :-2]) / tol).max()))
+            print(f"{name}: probe seed {probe_seed}: float64 replay at {worst_ratio:.3f} x the parameter criterion")
+            if worst_ratio <= 1.0:
+                break
+        else:
+            raise AssertionError("no probe seed on which the float64 replay meets the criterion")
+        out["probe_seed"] = np.asarray(probe_seed)
+        for it in range(n_iter):
+            out[f"it{it}_param_probe"] = ref[it]
+        out["final_param_probe"] = ref[n_iter]
+        npz(name + ".npz", **out)
 
 
 def g13_trained_flow():
@@ -813,7 +972,7 @@ def g13_trained_flow():
     npz("g13_trained_flow_mw6.npz", **out)
 
 
-GENERATORS_NOTE = "g14 needs tests/ on sys.path (helpers.seeded_oracle_flow)"
+GENERATORS_NOTE = "g14 / g18 need tests/ on sys.path (helpers.seeded_oracle_flow, helpers.param_probes)"
 sys.path.insert(0, os.path.dirname(HERE))
 
 
@@ -827,3 +986,6 @@ if __name__ == "__main__":
     g16_rejecting()
     # g17: six calls in a row from the shipped initial step size, tuning on (the step-size state carried from call to call)
     g17_step_size_trajectory()
+    # g18: the reference trainer at the widths of the fused minibatch tail (W padded to 320 / 256)
+    g18_trainer_traces_wide()
+    g18_rough_search()

@@ -105,6 +105,31 @@ def test_training_path_layout_matches_the_parameter_shapes_without_gpu():
     assert lib.fabhip_adam_workspace_bytes(1000) > 0
 
 
+def test_train_step_plan_follows_the_tape_tile_option_without_gpu():
+    """fabhip_train_step_plan (host-only): which tape kernel one fabhip_buffer_train_step call runs and whether the minibatch
+    arithmetic is fused into its tail - the 8-chain tiles need D <= 32 and a hidden width padded to 256 / 320, the tail in addition
+    FABHIP_OPT_TAPE_TILES = 0; bad arguments are rejected."""
+    from fab_torch_amd import _ops
+    lib = _lib.load()
+    out = (C.c_int64 * 3)()
+    key = _ops.OPT_TAPE_TILES
+    prev = lib.fabhip_get_option(key)
+    try:
+        for mode in (0, 8, 16):
+            lib.fabhip_set_option(key, mode)
+            for (D, K, W), G in (((32, 10, 320), 5), ((20, 3, 320), 5), ((32, 2, 288), 5), ((32, 3, 256), 4), ((6, 3, 240), 4),
+                                 ((31, 2, 186), 4)):
+                assert lib.fabhip_train_step_plan(D, K, W, out) == 0
+                assert list(out) == [16 if mode == 16 else 8, G, 1 if mode == 0 else 0], (mode, D, K, W, list(out))
+            for D, K, W in ((6, 3, 30), (60, 3, 240), (33, 2, 264), (32, 2, 512), (32, 10, 128)):
+                assert lib.fabhip_train_step_plan(D, K, W, out) == 0
+                assert (out[0], out[2]) == (16, 0), (mode, D, K, W, list(out))
+    finally:
+        lib.fabhip_set_option(key, prev)
+    assert lib.fabhip_train_step_plan(32, 10, 320, None) == -1
+    assert lib.fabhip_train_step_plan(65, 2, 32, out) != 0
+
+
 def test_anneal_coefficients_match_the_reference_formulas():
     lib = _lib.load()
     for beta in (0.0, 0.2, 1 / 3, 1.0):

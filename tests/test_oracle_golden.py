@@ -299,3 +299,49 @@ def test_oracle_trainer_iteration_vs_reference_traces(seed):
     assert np.array_equal(hmc.epsilons.numpy(), g["out_epsilons"])
     for k, v in nf.state_dict().items():
         assert close(v, g["final." + k], 1e-5), k
+
+
+MINIBATCH_KEYS = ("loss", "grad_norm", "w_adjust_mean", "w_adjust_min", "w_adjust_max", "log_q_x_mean")
+G18 = ("g18_trainer_w320_mild", "g18_trainer_w320_clip", "g18_trainer_w256_mild")
+
+
+@pytest.mark.parametrize("name", G18)
+def test_oracle_trainer_replays_the_wide_reference_traces(name):
+    """oracle/train.py replays the reference trainer at the widths of the fused minibatch tail (g18: D = 32, 10 layers, W = 320 in
+    a mild and a clipping regime; D = 6, W = 240) with the criteria of the g12 replay - sampled indices bit-exact, the rest 1e-5
+    (same eager CPU ops) - extended to EVERY minibatch (loss, the gradient norm as the reference's variable holds it, mean / min /
+    max of the weights before the clip, mean log q; clipped rows and whether the optimiser stepped exactly) and to the probes of
+    every parameter tensor at every iteration start and at the end.  This is what lets the GPU tests take full parameter tensors
+    and Adam moments from the oracle instead of from a file."""
+    from helpers import g18_oracle_replay, probes_close
+    g = load_golden(name + ".npz")
+    n_iter, n_batches, seed = int(g["n_iter"]), int(g["n_batches"]), int(g["probe_seed"])
+    holder = {}
+
+    def check(it, st):
+        ref = g[f"it{it}_param_probe"] if it < n_iter else g["final_param_probe"]
+        params = [st["params"][k] for k, _ in holder["names"]]
+        assert probes_close(params, seed, ref, 1e-5) == [], (it, probes_close(params, seed, ref, 1e-5))
+        if it < n_iter:
+            assert np.array_equal(st["eps"].numpy(), g[f"it{it}_eps"]) and np.array_equal(st["ceps"].numpy(), g[f"it{it}_ceps"])
+    from helpers import flow_from_g14
+    holder["names"] = list(flow_from_g14(g).named_parameters())
+    r = g18_oracle_replay(g, check)
+    for c, lw in enumerate(r["init_log_w"]):
+        assert close(lw, g[f"call{c}_log_w"], 1e-5)
+    clipped = 0
+    for it, out in enumerate(r["outs"]):
+        assert np.array_equal(out["indices"].numpy(), g[f"it{it}_indices"]), f"iteration {it}: sampled indices"
+        for key in ("loss", "grad_norm", "ess_ais", "log_Z", "w_adjust_mean", "log_q_x_mean"):
+            ref = float(g[f"it{it}_{key}"])
+            assert abs(out[key] - ref) <= 1e-5 * max(1.0, abs(ref)), (it, key, out[key], ref)
+        assert len(out["minibatches"]) == n_batches
+        for j, mb in enumerate(out["minibatches"]):
+            for key in MINIBATCH_KEYS:
+                ref = float(g[f"it{it}_mb{j}_{key}"])
+                assert abs(mb[key] - ref) <= 1e-5 * max(1.0, abs(ref)), (it, j, key, mb[key], ref)
+            assert mb["n_clipped"] == int(g[f"it{it}_mb{j}_n_clipped"]) and mb["stepped"] == int(g[f"it{it}_mb{j}_stepped"])
+            clipped += mb["n_clipped"]
+        assert close(out["buf_log_w"], g[f"it{it}_buf_log_w"], 1e-5) and close(out["buf_log_q_old"], g[f"it{it}_buf_log_q_old"], 1e-5)
+    assert (clipped > 0) == name.endswith("_clip")            # the regimes are what their names say
+    assert np.array_equal(r["hmc"].epsilons.numpy(), g["out_epsilons"])

@@ -1,6 +1,8 @@
-"""One FAB training iteration with the prioritised buffer on the reference's ManyWell-32 recipe, timed end to end and by phase.
+"""One FAB training iteration with the prioritised buffer on a MODIFIED version of the reference's ManyWell-32 recipe, timed end to
+end and by phase.  It is not the reference's recipe as shipped: float32 throughout, an initial HMC step size of 0.2 and the
+prioritised buffer switched on.
 
-Recipe (`/root/reference/experiments/config/many_well.yaml`: flow 10 x (16-320-320-32 + InvertibleAffine), batch 2048, M = 4,
+Recipe (the reference's `experiments/config/many_well.yaml`: flow 10 x (16-320-320-32 + InvertibleAffine), batch 2048, M = 4,
 HMC L = 5, alpha = 2, 8 minibatches per iteration (`n_batches_buffer_sampling`), buffer 512 000 / min 65 536, lr 3e-4,
 max_grad_norm 100, no weight clipping) through `fab_torch_amd.PrioritisedBufferTrainer.step` =
 `fab/train_with_prioritised_buffer.py:138-216`.  Timing: `iteration_ms` = N back-to-back `trainer.step` calls between two
