@@ -113,9 +113,9 @@ SYMBOLS = [
     "fabhip_flow_pack_train", "fabhip_flow_log_prob_tape_rows", "fabhip_train_step_workspace_bytes", "fabhip_buffer_train_step",
     "fabhip_buffer_add", "fabhip_buffer_sample_workspace_bytes", "fabhip_buffer_sample",
     "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
-    "fabhip_train_step_plan",
+    "fabhip_train_step_plan", "fabhip_resample_stream_workspace_bytes", "fabhip_resample_multinomial_stream",
 ]
-ABI_VERSION = 218          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 219          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -169,6 +169,9 @@ def _declare(lib):
     lib.fabhip_resample_multinomial.argtypes = [vp, i64, vp, i64, vp, vp, sz, vp]
     lib.fabhip_resample_systematic.argtypes = [vp, i64, dbl, i64, vp, vp, sz, vp]
     lib.fabhip_fixed_cdf.argtypes = [vp, i64, i32, vp, vp, sz, vp]
+    lib.fabhip_resample_stream_workspace_bytes.restype = sz
+    lib.fabhip_resample_stream_workspace_bytes.argtypes = [i64, i64]
+    lib.fabhip_resample_multinomial_stream.argtypes = [vp, i64, C.c_uint64, i64, i32, vp, vp, sz, vp]
     lib.fabhip_gather_rows.argtypes = [vp, vp, vp, i64, i64, vp]
     lib.fabhip_debug_timeline.argtypes = [vp, i32]
     lib.fabhip_flow_grad_floats.restype = i64

@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 218          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 219          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM = 1, 2
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -243,6 +243,10 @@ def _register_fakes():
 
     @rf("fabhip::resample_systematic")
     def _(log_w, u0, n_samples):
+        return log_w.new_empty((n_samples,), dtype=torch.int64)
+
+    @rf("fabhip::resample_multinomial_stream")
+    def _(log_w, seed, n_samples, order):
         return log_w.new_empty((n_samples,), dtype=torch.int64)
 
     @rf("fabhip::smc_decide")

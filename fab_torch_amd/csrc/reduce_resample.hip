@@ -1246,6 +1246,374 @@ __global__ __launch_bounds__(256) void k_emit_fill_runs(const unsigned long long
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Seeded streaming multinomial resampling (include/fabhip.h: fabhip_resample_multinomial_stream; tests/resample_stream_spec.py
+// restates it op for op).  The sorted values of ns iid uniforms are U_(k) = G_k / G_ns, G_k = e_0 + .. + e_k, with ns + 1
+// exponential spacings e_i = fixed-point -ln(u_i), u_i a pure function of (seed, i): no noise tensor, any wave regenerates the
+// spacings it needs in registers.  Sorted thresholds turn resampling into a MERGE of the draws with the CDF:
+//     draw k selects the first j with C_j G_ns > G_k total, i.e. weight j owns the draws [K(C_{j-1}), K(C_j)),
+//     K(C) = #{k < ns : G_k total < C G_ns}                                   (128-bit products, exact)
+//   k_emit_wave_sums / k_emit_prefix  (the systematic resampler's)  tile sums of W and their prefix, total
+//   k_ms_spacing_sums / k_emit_prefix / k_ms_tile_prefix            tile sums of e, inclusive prefix of every 1024-spacing tile
+//   k_ms_bounds   one wave per 1024-weight tile: K(c_start) - a 64-ary search of the spacing-tile prefixes, then an exact count
+//                 inside ONE regenerated tile
+//   k_ms_emit     the wave re-derives the CDF of its 1024 weights into LDS (as k_emit_systematic does), walks the spacing tiles
+//                 its draws [K0, K1) touch, regenerates each tile's G_k (16 consecutive per lane + one wave scan), turns G_k into
+//                 the integer threshold floor(G_k total / G_ns) - c_start (float64 estimate + one exact correction on the
+//                 wrapped 64-bit remainder) and bisects the LDS CDF; the indices leave through an LDS transpose as 32-byte
+//                 per-lane coalesced stores.  Weights that own >= 8192 draws are located exactly (two more K() evaluations),
+//                 published and filled grid-wide by k_emit_fill_runs; the wave jumps over the spacing tiles inside such a run.
+//   k_ms_shuffle  order = shuffled: out[k] = idx[pi(k)], pi the Feistel / cycle-walking bijection of k_random_order keyed by the seed
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned long long MS_GOLDEN = 0x9E3779B97F4A7C15ull, MS_MIX1 = 0xBF58476D1CE4E5B9ull, MS_MIX2 = 0x94D049BB133111EBull;
+constexpr long long MS_LN2_FIX = 186065279;             // round(ln 2 * 2^28)
+constexpr unsigned long long MS_KEY_BASE = 1ull << 40;  // counters of the permutation's round keys (beyond every spacing index)
+constexpr int MS_TILE = 1024;                           // spacings per tile (one wave: 16 consecutive per lane)
+constexpr int MS_CDF_LDS = (1024 + 64) * 8;             // the wave's relative CDF, rows of 16 + 1 pad (aliases the float staging)
+constexpr int MS_ITEM_LDS = (1024 + 64) * 4;            // the tile's selected items, rows of 16 + 1 pad
+constexpr int MS_GMAX = 32;                             // published giant runs remembered per wave
+constexpr int MS_WAVE_LDS = MS_CDF_LDS + MS_ITEM_LDS + 2 * MS_GMAX * 8;
+constexpr long MS_GIANT_MIN = 8192;                     // runs at least this long are published
+constexpr double MS_GIANT_EST = 16384.0;                // ... when the weight's EXPECTED run is at least this long
+static_assert(MS_CDF_LDS >= 64 * EM_FSTRIDE * 4, "float staging must fit under the CDF");
+
+__device__ __forceinline__ unsigned long long ms_hash(unsigned long long seed, unsigned long long i) {
+    unsigned long long z = seed + (i + 1ull) * MS_GOLDEN;
+    z = (z ^ (z >> 30)) * MS_MIX1;
+    z = (z ^ (z >> 27)) * MS_MIX2;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ unsigned ms_mix32(unsigned x) {              // (murmur3 finaliser, topk.hip: tk_mix)
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+
+// e_i: fixed-point (28 fractional bits) -ln of u = f 2^-(lz + 1), f the top 24 bits of the odd 32-bit word y as a float in
+// [1, 2).  Integer operations and individually rounded float32 multiplies / adds only (no contraction in this file).
+__device__ __forceinline__ unsigned long long ms_spacing(unsigned long long seed, unsigned long long i) {
+    const unsigned y = (unsigned)(ms_hash(seed, i) >> 32) | 1u;
+    const int lz = __clz((int)y);
+    const unsigned mant = (y << lz) >> 8;
+    const float f = (float)mant * 1.1920928955078125e-07f;            // exact
+    const bool red = f >= 1.41421354f;
+    const float g = red ? f * 0.5f : f;
+    const float t = g - 1.0f;                                         // exact
+    float p = 0.08743945509195328f;
+    p = p * t + -0.14377330243587494f;
+    p = p * t + 0.14949095249176025f;
+    p = p * t + -0.16560696065425873f;
+    p = p * t + 0.19956977665424347f;
+    p = p * t + -0.2500215470790863f;
+    p = p * t + 0.3333418369293213f;
+    p = p * t + -0.49999988079071045f;
+    p = p * t + 1.0f;
+    p = p * t;
+    const long long e = (long long)(lz + 1 - (red ? 1 : 0)) * MS_LN2_FIX - (long long)(int)rintf(p * 268435456.0f);
+    return e < 1 ? 1ull : (unsigned long long)e;
+}
+
+struct U128 { unsigned long long hi, lo; };
+__device__ __forceinline__ U128 mul128(unsigned long long a, unsigned long long b) { return U128{__umul64hi(a, b), a * b}; }
+__device__ __forceinline__ bool lt128(const U128& a, const U128& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+__device__ __forceinline__ int ms_pad(int p) { return p + (p >> 4); }
+
+__global__ __launch_bounds__(64 * EM_NW) void k_ms_spacing_sums(unsigned long long seed, long ns,
+                                                                unsigned long long* __restrict__ wave_sum,
+                                                                unsigned long long* __restrict__ block_sum) {
+    __shared__ unsigned long long wsum[EM_NW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long wt = (long)blockIdx.x * EM_NW + wave;
+    const long base = wt * MS_TILE;
+    unsigned long long acc = 0ull;
+#pragma unroll 4
+    for (int j = 0; j < MS_TILE / 64; ++j) {
+        const long i = base + 64 * j + lane;
+        if (i <= ns) acc += ms_spacing(seed, (unsigned long long)i);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += shfl_u64(acc, lane ^ off);
+    if (lane == 0) { wsum[wave] = acc; if (base <= ns) wave_sum[wt] = acc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long b = 0ull;
+        for (int w = 0; w < EM_NW; ++w) b += wsum[w];
+        block_sum[blockIdx.x] = b;
+    }
+}
+
+// inclusive prefix at the end of every spacing tile: tinc[t] = G_{min(1024 t + 1023, ns)}
+__global__ __launch_bounds__(256) void k_ms_tile_prefix(const unsigned long long* __restrict__ wave_sum,
+                                                        const unsigned long long* __restrict__ block_excl, long nt,
+                                                        unsigned long long* __restrict__ tinc) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    unsigned long long s = block_excl[t / EM_NW];
+    for (long w = t / EM_NW * EM_NW; w <= t; ++w) s += wave_sum[w];
+    tinc[t] = s;
+}
+
+// G_k of the spacings of tile t, 16 consecutive per lane: g[j] = G_{1024 t + 16 lane + j} (indices beyond ns repeat G_ns)
+__device__ __forceinline__ void ms_tile_sums(unsigned long long seed, long ns, long t, const unsigned long long* __restrict__ tinc,
+                                             int lane, unsigned long long (&g)[16]) {
+    const long i0 = t * MS_TILE + 16 * lane;
+    unsigned long long acc = 0ull;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if (i0 + j <= ns) acc += ms_spacing(seed, (unsigned long long)(i0 + j));
+        g[j] = acc;
+    }
+    unsigned long long incl = acc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o = shfl_up_u64(incl, off);
+        if (lane >= off) incl += o;
+    }
+    const unsigned long long off0 = incl - acc + (t > 0 ? tinc[t - 1] : 0ull);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) g[j] += off0;
+}
+
+// K(C) = #{k < ns : G_k total < C G_ns}, C wave-uniform, the whole wave calls it.  64-ary search for the first spacing tile
+// whose last G reaches C (the last tile always does: G_ns total >= C G_ns), then the exact count inside that tile.
+__device__ __forceinline__ long ms_count_below(unsigned long long C, unsigned long long total, unsigned long long Gn,
+                                               unsigned long long seed, long ns, const unsigned long long* __restrict__ tinc,
+                                               long nte, int lane) {
+    if (C == 0ull) return 0;
+    if (C >= total) return ns;
+    const U128 rhs = mul128(C, Gn);
+    long lo = 0, hi = nte;
+    while (hi - lo > 1) {
+        const long step = (hi - lo + 63) >> 6;
+        long i = lo + (long)(lane + 1) * step - 1;
+        if (i > hi - 1) i = hi - 1;
+        const bool reached = !lt128(mul128(tinc[i], total), rhs);
+        const unsigned long long m = __ballot(reached);
+        if (m == 0ull) return ns;                          // (cannot happen: lane 63 probes hi - 1)
+        const int f = __ffsll((long long)m) - 1;
+        lo += (long)f * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    unsigned long long g[16];
+    ms_tile_sums(seed, ns, lo, tinc, lane, g);
+    const long i0 = lo * MS_TILE + 16 * lane;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cnt += (i0 + j < ns && lt128(mul128(g[j], total), rhs)) ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    return lo * MS_TILE + cnt;
+}
+
+// kb[w] = K(c_start of weight tile w), w = 0 .. nwt (kb[nwt] = ns); nothing when every weight is zero
+__global__ __launch_bounds__(64 * EM_NW) void k_ms_bounds(const unsigned long long* __restrict__ wave_sum,
+                                                          const unsigned long long* __restrict__ block_excl, long nwt,
+                                                          const unsigned long long* __restrict__ strata_w,
+                                                          const unsigned long long* __restrict__ strata_e,
+                                                          unsigned long long seed, long ns,
+                                                          const unsigned long long* __restrict__ tinc, long nte,
+                                                          long long* __restrict__ kb) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long w = (long)blockIdx.x * EM_NW + wave;
+    const unsigned long long total = strata_w[0], Gn = strata_e[0];
+    if (w > nwt || total == 0ull) return;
+    long k = ns;
+    if (w < nwt) {
+        unsigned long long c = block_excl[w / EM_NW];
+        for (long v = w / EM_NW * EM_NW; v < w; ++v) c += wave_sum[v];
+        k = ms_count_below(c, total, Gn, seed, ns, tinc, nte, lane);
+    }
+    if (lane == 0) kb[w] = k;
+}
+
+__global__ __launch_bounds__(64 * EM_NW) void k_ms_emit(const float* __restrict__ lw, long n, const float* __restrict__ max_val,
+                                                        const unsigned long long* __restrict__ wave_sum,
+                                                        const unsigned long long* __restrict__ block_excl,
+                                                        const unsigned long long* __restrict__ strata_w,
+                                                        const unsigned long long* __restrict__ strata_e,
+                                                        unsigned long long seed, long ns,
+                                                        const unsigned long long* __restrict__ tinc, long nte,
+                                                        const long long* __restrict__ kb, long long* __restrict__ idx,
+                                                        unsigned long long* __restrict__ giant_count,
+                                                        long long* __restrict__ giant_desc, long giant_cap) {
+    __shared__ __attribute__((aligned(16))) unsigned char ms_lds[EM_NW * MS_WAVE_LDS];
+    typedef long long i64x2 __attribute__((ext_vector_type(2)));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long wt = (long)blockIdx.x * EM_NW + wave;
+    const long wbase = wt * EM_WAVE_ITEMS;
+    if (wbase >= n) return;
+    const unsigned long long total = strata_w[0];
+    if (total == 0ull) {                                   // all weights zero: every draw maps to the last index
+        if (wt == 0)
+            for (long k = lane; k < ns; k += 64) idx[k] = n - 1;
+        return;
+    }
+    const long K0 = kb[wt], K1 = kb[wt + 1];               // this wave's draws (wave-uniform)
+    if (K1 <= K0) return;
+    const unsigned long long Gn = strata_e[0];
+    unsigned char* wl = ms_lds + (size_t)wave * MS_WAVE_LDS;
+    float* wf = reinterpret_cast<float*>(wl);
+    unsigned long long* crel = reinterpret_cast<unsigned long long*>(wl);
+    int* itm = reinterpret_cast<int*>(wl + MS_CDF_LDS);
+    long long* ga = reinterpret_cast<long long*>(wl + MS_CDF_LDS + MS_ITEM_LDS);
+    long long* gb = ga + MS_GMAX;
+    const float mx = max_val[0];
+    unsigned long long c_start = block_excl[blockIdx.x];
+    for (int w = 0; w < wave; ++w) c_start += wave_sum[(long)blockIdx.x * EM_NW + w];
+    // ---- CDF of this wave's 1024 weights relative to c_start: lane owns items [16 lane, 16 lane + 16) (k_emit_systematic) ----
+    if (wbase + EM_WAVE_ITEMS <= n && (((size_t)lw & 15) == 0)) {
+        float4 x[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) x[h] = *reinterpret_cast<const float4*>(lw + wbase + h * 256 + lane * 4);
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+            *reinterpret_cast<float4*>(wf + (16 * h + (lane >> 2)) * EM_FSTRIDE + 4 * (lane & 3)) = x[h];
+    } else {
+        for (int i = lane; i < EM_WAVE_ITEMS; i += 64)
+            wf[(i >> 4) * EM_FSTRIDE + (i & 15)] = (wbase + i < n) ? lw[wbase + i] : -INFINITY;
+    }
+    __builtin_amdgcn_wave_barrier();
+    unsigned long long run[16];
+    unsigned long long acc = 0ull;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 y = *reinterpret_cast<const float4*>(wf + lane * EM_FSTRIDE + 4 * k);
+        acc += fixed_weight(y.x, mx); run[4 * k + 0] = acc;
+        acc += fixed_weight(y.y, mx); run[4 * k + 1] = acc;
+        acc += fixed_weight(y.z, mx); run[4 * k + 2] = acc;
+        acc += fixed_weight(y.w, mx); run[4 * k + 3] = acc;
+    }
+    unsigned long long incl = acc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o = shfl_up_u64(incl, off);
+        if (lane >= off) incl += o;
+    }
+    const unsigned long long lane_off = incl - acc;
+    // weights whose EXPECTED run is long: candidates for the grid-wide fill (decided exactly below)
+    unsigned cand = 0u;
+    if (K1 - K0 >= MS_GIANT_MIN) {                         // wave-uniform
+        const double scale = (double)ns / (double)total;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned long long wj = run[j] - (j ? run[j - 1] : 0ull);
+            if ((double)wj * scale >= MS_GIANT_EST) cand |= 1u << j;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();                       // every lane is done reading the float staging
+#pragma unroll
+    for (int j = 0; j < 16; ++j) crel[17 * lane + j] = lane_off + run[j];
+    __builtin_amdgcn_wave_barrier();
+    int gcnt = 0;                                          // published runs of this wave (wave-uniform)
+    while (gcnt < MS_GMAX) {
+        const unsigned long long m = __ballot(cand != 0u);
+        if (m == 0ull) break;
+        const int src = __ffsll((long long)m) - 1;
+        const unsigned cm = (unsigned)__shfl((int)cand, src);
+        const int j = __ffs((int)cm) - 1;
+        if (lane == src) cand &= cand - 1u;
+        const int pos = 16 * src + j;
+        const unsigned long long cj = crel[ms_pad(pos)], cp = pos ? crel[ms_pad(pos - 1)] : 0ull;
+        const long a = ms_count_below(c_start + cp, total, Gn, seed, ns, tinc, nte, lane);
+        const long b = ms_count_below(c_start + cj, total, Gn, seed, ns, tinc, nte, lane);
+        if (b - a < MS_GIANT_MIN) continue;
+        unsigned long long slot = 0ull;
+        if (lane == 0) slot = atomicAdd(giant_count, 1ull);
+        slot = shfl_u64(slot, 0);
+        if ((long)slot >= giant_cap) break;                // (list full: the run stays with this wave)
+        if (lane == 0) {
+            const long id = wbase + pos;
+            giant_desc[3 * slot] = a; giant_desc[3 * slot + 1] = b; giant_desc[3 * slot + 2] = id < n ? id : n - 1;
+            ga[gcnt] = a; gb[gcnt] = b;
+        }
+        ++gcnt;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- the spacing tiles this wave's draws touch ----
+    const U128 Bc = mul128(c_start, Gn);
+    const double invGn = 1.0 / (double)Gn;
+    const long t_last = (K1 - 1) / MS_TILE;
+    for (long t = K0 / MS_TILE; t <= t_last;) {
+        if (gcnt > 0) {                                    // draws of this tile all inside ONE published run: jump to its end
+            const long dlo = K0 > t * MS_TILE ? K0 : t * MS_TILE, dhi = K1 < (t + 1) * MS_TILE ? K1 : (t + 1) * MS_TILE;
+            const long long ra = lane < gcnt ? ga[lane] : 0, rb = lane < gcnt ? gb[lane] : 0;
+            const unsigned long long m = __ballot(lane < gcnt && ra <= dlo && rb >= dhi);
+            if (m != 0ull) {
+                const long e = shfl_i64(rb, __ffsll((long long)m) - 1);
+                if (e >= K1) break;
+                t = e / MS_TILE;
+                continue;
+            }
+        }
+        unsigned long long g[16];
+        ms_tile_sums(seed, ns, t, tinc, lane, g);
+        const long k0 = t * MS_TILE + 16 * lane;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const long k = k0 + j;
+            const bool inr = k >= K0 && k < K1;
+            // q = floor(G_k total / G_ns) - c_start = floor((G_k total - c_start G_ns) / G_ns) in [0, wave total)
+            const U128 A = mul128(g[j], total);
+            const unsigned long long rlo = A.lo - Bc.lo, rhi = A.hi - Bc.hi - (A.lo < Bc.lo ? 1ull : 0ull);
+            const double est = inr ? ((double)rhi * 18446744073709551616.0 + (double)rlo) * invGn : 0.0;
+            unsigned long long q = (unsigned long long)est;                     // off by at most one
+            const long long rem = (long long)(rlo - q * Gn);                   // |R - q G_ns| < 2 G_ns < 2^63: the wrap is exact
+            if (rem < 0) --q;
+            else if (rem >= (long long)Gn) ++q;
+            if (!inr) q = 0ull;
+            int pos = 0;                                   // entries <= q  =  first entry > q
+#pragma unroll
+            for (int s = 512; s > 0; s >>= 1) {
+                const int p = pos + s - 1;
+                if (crel[ms_pad(p)] <= q) pos += s;
+            }
+            itm[17 * lane + j] = pos < 1023 ? pos : 1023;
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int p = 4 * lane; p < MS_TILE; p += 256) {
+            const long k = t * MS_TILE + p;
+            const int b0 = ms_pad(p);
+            long r0 = wbase + itm[b0], r1 = wbase + itm[b0 + 1], r2 = wbase + itm[b0 + 2], r3 = wbase + itm[b0 + 3];
+            r0 = r0 < n ? r0 : n - 1; r1 = r1 < n ? r1 : n - 1; r2 = r2 < n ? r2 : n - 1; r3 = r3 < n ? r3 : n - 1;
+            if (k >= K0 && k + 3 < K1) {
+                i64x2* o = reinterpret_cast<i64x2*>(idx + k);
+                o[0] = (i64x2){r0, r1};
+                o[1] = (i64x2){r2, r3};
+            } else {
+                if (k >= K0 && k < K1) idx[k] = r0;
+                if (k + 1 >= K0 && k + 1 < K1) idx[k + 1] = r1;
+                if (k + 2 >= K0 && k + 2 < K1) idx[k + 2] = r2;
+                if (k + 3 >= K0 && k + 3 < K1) idx[k + 3] = r3;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        ++t;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ms_shuffle(const long long* __restrict__ idx_in, long ns, unsigned long long seed,
+                                                    long long* __restrict__ idx_out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns) return;
+    int bits = 2;
+    while ((1l << bits) < ns) ++bits;
+    const int lb = bits >> 1, rb = bits - lb;
+    const unsigned lm = (1u << lb) - 1u, rm = (1u << rb) - 1u;
+    unsigned key[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) key[j] = (unsigned)ms_hash(seed, MS_KEY_BASE + (unsigned long long)j);
+    unsigned long v = (unsigned long)i;
+    do {
+        unsigned l = (unsigned)(v >> rb) & lm, r = (unsigned)v & rm;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j & 1) r ^= ms_mix32(l ^ key[j]) & rm;
+            else l ^= ms_mix32(r ^ key[j]) & lm;
+        }
+        v = ((unsigned long)l << rb) | r;
+    } while ((long)v >= ns);
+    idx_out[i] = idx_in[v];
+}
+
 __global__ void k_gather_rows(const float* __restrict__ src, const long long* __restrict__ idx, float* __restrict__ dst,
                               long n_out, long row_len) {
     if ((row_len & 3) == 0 && ((size_t)src & 15) == 0 && ((size_t)dst & 15) == 0) {
@@ -1599,6 +1967,77 @@ int fabhip_resample_systematic(const float* log_w, int64_t n, double u0, int64_t
                        (long)n_samples, (long long*)idx, giant_count, giant_desc, giant_cap);
     if (giant_cap > 0 && n_samples >= EM_GIANT)
         hipLaunchKernelGGL(k_emit_fill_runs, dim3(256), dim3(256), 0, st, giant_count, giant_desc, giant_cap,
+                           (long long*)idx);
+    return check_launch();
+}
+
+namespace {
+struct StreamWs {         // workspace layout of the streaming multinomial resampler (all 256-byte aligned)
+    float* max_part; float* max_val;
+    unsigned long long *w_wave, *w_block, *w_excl, *w_strata;      // weights: tile sums, block sums, prefix, {total, ..} + run counter
+    unsigned long long *e_wave, *e_block, *e_excl, *e_strata;      // spacings: the same
+    unsigned long long* tinc;                                      // [nte] inclusive prefix at the end of every spacing tile
+    long long* kb;                                                 // [nwt + 1] first draw of every weight tile
+    long long* giant_desc;                                         // [3 giant_cap]
+    long long* sorted;                                             // [n_samples] the sorted indices of order = shuffled
+    long nwt, nbk, nte, nbe, giant_cap;
+    size_t bytes;
+};
+StreamWs carve_stream_ws(void* workspace, long n, long ns) {
+    StreamWs s;
+    s.nwt = (n + EM_WAVE_ITEMS - 1) / EM_WAVE_ITEMS; s.nbk = (n + EM_BLOCK - 1) / EM_BLOCK;
+    s.nte = ns / MS_TILE + 1;                                      // spacings 0 .. ns
+    s.nbe = (s.nte + EM_NW - 1) / EM_NW;
+    s.giant_cap = ns / MS_GIANT_MIN + 1;
+    char* p = (char*)workspace;
+    auto take = [&](size_t b) { char* q = p; p += al256(b); return q; };
+    s.max_part = (float*)take(1024 * 4); s.max_val = (float*)take(4);
+    s.w_wave = (unsigned long long*)take((size_t)s.nbk * EM_NW * 8); s.w_block = (unsigned long long*)take((size_t)s.nbk * 8);
+    s.w_excl = (unsigned long long*)take((size_t)s.nbk * 8); s.w_strata = (unsigned long long*)take(64);
+    s.e_wave = (unsigned long long*)take((size_t)s.nbe * EM_NW * 8); s.e_block = (unsigned long long*)take((size_t)s.nbe * 8);
+    s.e_excl = (unsigned long long*)take((size_t)s.nbe * 8); s.e_strata = (unsigned long long*)take(64);
+    s.tinc = (unsigned long long*)take((size_t)s.nte * 8);
+    s.kb = (long long*)take((size_t)(s.nwt + 1) * 8);
+    s.giant_desc = (long long*)take((size_t)s.giant_cap * 24);
+    s.sorted = (long long*)take((size_t)ns * 8);
+    s.bytes = (size_t)(p - (char*)workspace);
+    return s;
+}
+}  // namespace
+
+size_t fabhip_resample_stream_workspace_bytes(int64_t n, int64_t n_samples) {
+    if (n < 1 || n_samples < 1 || n_samples > FABHIP_STREAM_MAX_SAMPLES) return 0;
+    return carve_stream_ws(nullptr, (long)n, (long)n_samples).bytes;
+}
+
+int fabhip_resample_multinomial_stream(const float* log_w, int64_t n, uint64_t seed, int64_t n_samples, int32_t order,
+                                       int64_t* idx, void* workspace, size_t workspace_bytes, fabhip_stream_t stream) {
+    if (!log_w || !idx || !workspace || n < 1 || n_samples < 1) return FABHIP_EINVAL;
+    if (order != FABHIP_ORDER_SORTED && order != FABHIP_ORDER_SHUFFLED) return FABHIP_EINVAL;
+    if (n_samples > FABHIP_STREAM_MAX_SAMPLES) return FABHIP_EINVAL;
+    if (((size_t)workspace & 255) != 0) return FABHIP_EINVAL;
+    if (workspace_bytes < fabhip_resample_stream_workspace_bytes(n, n_samples)) return FABHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const long ns = (long)n_samples;
+    const StreamWs s = carve_stream_ws(workspace, (long)n, ns);
+    long long* out = order == FABHIP_ORDER_SHUFFLED ? s.sorted : (long long*)idx;
+    const int mb = grid_for(n, 256 * 16, 1024);
+    hipLaunchKernelGGL(k_max_partial, dim3(mb), dim3(256), 0, st, log_w, (long)n, s.max_part);
+    hipLaunchKernelGGL(k_max_final, dim3(1), dim3(256), 0, st, s.max_part, mb, s.max_val);
+    const dim3 block(64 * EM_NW);
+    hipLaunchKernelGGL(k_emit_wave_sums, dim3((unsigned)s.nbk), block, 0, st, log_w, (long)n, s.max_val, s.w_wave, s.w_block);
+    hipLaunchKernelGGL(k_emit_prefix, dim3(1), dim3(1024), 0, st, s.w_block, s.nbk, s.w_excl, 0.0, ns, s.w_strata, s.w_strata + 4);
+    hipLaunchKernelGGL(k_ms_spacing_sums, dim3((unsigned)s.nbe), block, 0, st, (unsigned long long)seed, ns, s.e_wave, s.e_block);
+    hipLaunchKernelGGL(k_emit_prefix, dim3(1), dim3(1024), 0, st, s.e_block, s.nbe, s.e_excl, 0.0, ns, s.e_strata, s.e_strata + 4);
+    hipLaunchKernelGGL(k_ms_tile_prefix, dim3((unsigned)((s.nte + 255) / 256)), dim3(256), 0, st, s.e_wave, s.e_excl, s.nte, s.tinc);
+    hipLaunchKernelGGL(k_ms_bounds, dim3((unsigned)((s.nwt + 1 + EM_NW - 1) / EM_NW)), block, 0, st, s.w_wave, s.w_excl, s.nwt,
+                       s.w_strata, s.e_strata, (unsigned long long)seed, ns, s.tinc, s.nte, s.kb);
+    hipLaunchKernelGGL(k_ms_emit, dim3((unsigned)s.nbk), block, 0, st, log_w, (long)n, s.max_val, s.w_wave, s.w_excl, s.w_strata,
+                       s.e_strata, (unsigned long long)seed, ns, s.tinc, s.nte, s.kb, out, s.w_strata + 4, s.giant_desc, s.giant_cap);
+    if (ns >= MS_GIANT_MIN)
+        hipLaunchKernelGGL(k_emit_fill_runs, dim3(256), dim3(256), 0, st, s.w_strata + 4, s.giant_desc, s.giant_cap, out);
+    if (order == FABHIP_ORDER_SHUFFLED)
+        hipLaunchKernelGGL(k_ms_shuffle, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, out, ns, (unsigned long long)seed,
                            (long long*)idx);
     return check_launch();
 }

@@ -1323,6 +1323,20 @@ Tensor resample_systematic(const Tensor& log_w, double u0, int64_t n_samples) {
     return idx;
 }
 
+// seeded streaming multinomial: the 64 bits of `seed` are the C ABI's uint64 seed (order: FABHIP_ORDER_*)
+Tensor resample_multinomial_stream(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
+    c10::DeviceGuard g(log_w.device());
+    const int64_t n = log_w.numel();
+    TORCH_CHECK(n_samples >= 1, "fabhip::resample_multinomial_stream: n_samples must be >= 1");
+    Tensor idx = at::empty({n_samples}, log_w.options().dtype(at::kLong));
+    const size_t nb = fabhip_resample_stream_workspace_bytes(n, n_samples);
+    Tensor ws = scratch(nb, log_w);
+    chk(fabhip_resample_multinomial_stream(fp(log_w, "log_w"), n, (uint64_t)seed, n_samples, (int32_t)order,
+                                           idx.data_ptr<int64_t>(), aligned(ws), nb, stream_of(log_w)),
+        "resample_multinomial_stream");
+    return idx;
+}
+
 Tensor multinomial_torch(const Tensor& probs, const Tensor& u) {
     c10::DeviceGuard g(probs.device());
     need(u, at::kDouble, "u");
@@ -1521,6 +1535,7 @@ TORCH_LIBRARY(fabhip, m) {
     m.def("fixed_cdf(Tensor log_w, Tensor(a!)? workspace) -> Tensor(a!)");
     m.def("resample_multinomial(Tensor log_w, Tensor u) -> Tensor");
     m.def("resample_systematic(Tensor log_w, float u0, int n_samples) -> Tensor");
+    m.def("resample_multinomial_stream(Tensor log_w, int seed, int n_samples, int order) -> Tensor");
     m.def("multinomial_torch(Tensor probs, Tensor u) -> Tensor");
     m.def("gather_rows(Tensor src, Tensor idx) -> Tensor");
     m.def("topk(Tensor keys, int k, bool sorted) -> Tensor");
@@ -1574,6 +1589,7 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("fixed_cdf", fixed_cdf);
     m.impl("resample_multinomial", resample_multinomial);
     m.impl("resample_systematic", resample_systematic);
+    m.impl("resample_multinomial_stream", resample_multinomial_stream);
     m.impl("multinomial_torch", multinomial_torch);
     m.impl("gather_rows", gather_rows);
     m.impl("topk", topk);

@@ -4,6 +4,8 @@
 * `resample(..., method="multinomial")`: scalable fixed-point CDF (single-pass decoupled-look-back
   scan) + two-level binary search + vectorised row gather; uniforms are float64 draws from torch's
   device generator.
+* `resample(..., method="multinomial_stream", seed=s)`: seeded streaming multinomial - the sorted draws are generated on
+  the fly from exponential spacings (a counter-based hash of the seed) and merged with the CDF; no tensor of uniforms.
 * `multinomial_torch_compat(probs, u)`: bit-exact restatement of torch's CPU multinomial given the
   probabilities and the float64 uniforms it consumed (parity with the reference's RNG path).
 """
@@ -33,6 +35,28 @@ def systematic_indices(log_w: torch.Tensor, u0: float = None, n_samples: int = N
     return _ops.load().resample_systematic(lw, float(u0), ns)
 
 
+STREAM_ORDERS = {"sorted": 0, "shuffled": 1}          # FABHIP_ORDER_*
+
+
+def multinomial_stream_indices(log_w: torch.Tensor, n_samples: int = None, seed: int = None,
+                               order: str = "sorted") -> torch.Tensor:
+    """Multinomial resampling indices from `(log_w, seed)` alone (include/fabhip.h: fabhip_resample_multinomial_stream).
+    `order="sorted"`: non-decreasing indices (what a row gather needs, like `systematic_indices`); `order="shuffled"`: the same
+    indices in a seeded random order - an exchangeable sample, as `torch.multinomial` gives.  `seed=None` draws 64 bits from
+    torch's CPU generator; the same `(log_w, n_samples, seed, order)` gives the same indices on any device."""
+    _ops.require_device(log_w, "log_w")
+    if order not in STREAM_ORDERS:
+        raise _ops.FabhipError(f"order must be 'sorted' or 'shuffled' (got {order!r})")
+    lw = log_w.detach().contiguous().float()
+    ns = lw.shape[0] if n_samples is None else int(n_samples)
+    if seed is None:
+        seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (), dtype=torch.int64))
+    seed = int(seed) & ((1 << 64) - 1)
+    if seed >= 1 << 63:                                  # the op takes the 64 bits as a signed integer
+        seed -= 1 << 64
+    return _ops.load().resample_multinomial_stream(lw, seed, ns, STREAM_ORDERS[order])
+
+
 def multinomial_torch_compat(probs: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     _ops.require_device(probs, "probs")
     return _ops.load().multinomial_torch(probs.detach().contiguous().float(), u.contiguous().double())
@@ -43,9 +67,13 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return _ops.load().gather_rows(src.contiguous().float(), idx.contiguous())
 
 
-def resample(x_or_point: Union[Point, torch.Tensor], log_w: torch.Tensor, method: str = "multinomial"):
-    """Resample points according to the log weights (same call shape as the reference)."""
-    idx = multinomial_indices(log_w) if method == "multinomial" else systematic_indices(log_w)
+def resample(x_or_point: Union[Point, torch.Tensor], log_w: torch.Tensor, method: str = "multinomial", seed: int = None):
+    """Resample points according to the log weights (same call shape as the reference).  `seed` belongs to
+    `method="multinomial_stream"` (the other methods draw from torch's generators)."""
+    if method == "multinomial_stream":
+        idx = multinomial_stream_indices(log_w, seed=seed)
+    else:
+        idx = multinomial_indices(log_w) if method == "multinomial" else systematic_indices(log_w)
     if isinstance(x_or_point, Point):
         p = x_or_point
         g = lambda t: None if t is None else gather_rows(t, idx)

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 218
+#define FABHIP_ABI_VERSION 219
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -753,6 +753,37 @@ int fabhip_resample_multinomial(const float* log_w, int64_t n, const double* u, 
                                 fabhip_stream_t stream);
 int fabhip_resample_systematic(const float* log_w, int64_t n, double u0, int64_t n_samples, int64_t* idx,
                                void* workspace, size_t workspace_bytes, fabhip_stream_t stream);
+/* Seeded streaming multinomial resampler: multinomial resampling from (log_w, seed) alone - no tensor of uniforms, no CDF and
+ * no array of thresholds in HBM.  The definition is the project's own (tests/resample_stream_spec.py restates it; the device
+ * follows it bit for bit on any launch geometry):
+ *   W, C, total: the fixed-point weights and CDF above (non-finite rows weigh 0); total == 0: every index is n - 1.
+ *   spacing i = 0 .. n_samples:  z = seed + (i + 1) * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB;  r = z ^ z >> 31   (64-bit, the splitmix64 finaliser);  y = (r >> 32) | 1,
+ *     lz = clz32(y), f = float(((y << lz) mod 2^32) >> 8) * 2^-23 in [1, 2), u_i = f * 2^-(lz + 1) in (0, 1);
+ *     e_i = max(1, K * 186065279 - rint(p(g - 1) * 2^28)),  g = f >= 1.41421354f ? f / 2 : f,  K = lz + 1 - (f >= 1.41421354f),
+ *     p(t) = t (1 + t (c7 + .. t c0)) a float32 Horner form of ln(1 + t) with individually rounded operations and the
+ *     coefficients 0.08743945509195328, -0.14377330243587494, 0.14949095249176025, -0.16560696065425873, 0.19956977665424347,
+ *     -0.2500215470790863, 0.3333418369293213, -0.49999988079071045, 1 (highest first): e_i is -ln(u_i) with 28 fractional
+ *     bits, |e_i 2^-28 + ln u_i| <= 1.3e-7, e_i < 2^33.
+ *   G_k = e_0 + .. + e_k (exact); G_k / G_ns, k < n_samples, are distributed as the SORTED values of n_samples iid uniforms.
+ *   sorted draw k:  idx_k = first j with C_j * G_ns > G_k * total   (128-bit products; non-decreasing in k).
+ *   order = FABHIP_ORDER_SORTED returns idx (what the systematic resampler returns: all a row gather needs);
+ *   order = FABHIP_ORDER_SHUFFLED returns out[k] = idx[pi(k)], pi the Feistel / cycle-walking bijection of [0, n_samples) that
+ *   fabhip_topk's random order uses, its four round keys the low 32 bits of r for i = 2^40 + j: an exchangeable multinomial
+ *   sample, as torch.multinomial gives.
+ * n_samples <= FABHIP_STREAM_MAX_SAMPLES keeps G_ns < 2^62; more is FABHIP_EINVAL, like n < 1, n_samples < 1, an unknown
+ * order, a NULL pointer or a workspace that is not 256-byte aligned; a workspace smaller than
+ * fabhip_resample_stream_workspace_bytes(n, n_samples) (0 for arguments the call refuses) is FABHIP_ENOSPC.  All of it is
+ * checked before any launch and without touching a device.  The caller owns log_w [n], idx [n_samples] and the workspace
+ * (device memory); nothing is allocated, nothing synchronises, every launch goes to `stream`.
+ * Traffic, order = sorted: log_w three times (maximum, tile sums, merge), 8 n_samples bytes of indices, and per 1024
+ * weights / 1024 draws a few 8-byte prefix words - the systematic call's 12 n + 8 n_samples. */
+#define FABHIP_ORDER_SORTED 0
+#define FABHIP_ORDER_SHUFFLED 1
+#define FABHIP_STREAM_MAX_SAMPLES ((int64_t)((1ll << 29) - 1))
+size_t fabhip_resample_stream_workspace_bytes(int64_t n, int64_t n_samples);
+int fabhip_resample_multinomial_stream(const float* log_w, int64_t n, uint64_t seed, int64_t n_samples, int32_t order,
+                                       int64_t* idx, void* workspace, size_t workspace_bytes, fabhip_stream_t stream);
 /* dst[k][:] = src[idx[k]][:]  (Point.__getitem__ / tensor indexing used by resample) */
 int fabhip_gather_rows(const float* src, const int64_t* idx, float* dst, int64_t n_out, int64_t row_len,
                        fabhip_stream_t stream);

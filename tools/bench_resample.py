@@ -1,42 +1,82 @@
-"""Resample pipeline at N = 2^26 (HBM roofline size): per-stage HIP-event timings through the custom ops."""
-import json, sys, os
+"""Resamplers side by side in ONE process, alternating: HIP-event times through the custom ops, log_w ~ 3 N(0, 1) seed 0 (what
+bench.py: resample_rooflines uses), N = n_samples.  Per size and method: median and min..max of the calls, algorithmic bytes,
+GB/s and the share of the HBM peak.
+
+    python tools/bench_resample.py [--sizes 2048,16384,512000,1048576,16777216,67108864] [--calls 24] [--rounds 3] [--out FILE]
+
+Methods: multinomial_with_rand (torch.rand(float64) + fabhip_resample_multinomial, what `resample()` does by default),
+multinomial (uniforms given), systematic, stream_sorted, stream_shuffled (fabhip_resample_multinomial_stream).
+`--only METHOD --calls K` runs one method alone (for a kernel trace of its own)."""
+import argparse
+import json
+import os
+import sys
+
 import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import fab_torch_amd as fa
-from fab_torch_amd import _ops
+from fab_torch_amd import _ops  # noqa: E402
 
-def timeit(fn, n=20, warm=3):
-    for _ in range(warm):
-        fn()
+PEAK_HBM_TBPS = 8.0            # MI355X HBM3E spec (bench.py uses the same figure)
+
+
+def times(fn, n):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
     ev[0].record()
     for i in range(n):
-        fn(); ev[i + 1].record()
+        fn()
+        ev[i + 1].record()
     torch.cuda.synchronize()
-    ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(n))
-    return ms[n // 2] * 1e-3
+    return [ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in range(n)]
+
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="2048,16384,512000,1048576,16777216,67108864")
+    ap.add_argument("--calls", type=int, default=24)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
     ops = _ops.load()
-    N = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 26
-    g = torch.Generator(device="cuda").manual_seed(0)
-    lw = torch.randn(N, device="cuda", generator=g) * 3
-    out = {"N": N}
-    ws = ops.fixed_cdf(lw, None)
-    t = timeit(lambda: ops.fixed_cdf(lw, ws))
-    out["scan_only"] = {"s": t, "alg_bytes": 12 * N, "TBps": 12 * N / t / 1e12}
-    t = timeit(lambda: ops.fixed_cdf(lw, None))
-    out["max_plus_scan"] = {"s": t, "alg_bytes": 12 * N, "TBps": 12 * N / t / 1e12}
-    t = timeit(lambda: ops.resample_systematic(lw, 0.3, N))
-    out["systematic_fused_e2e"] = {"s": t, "alg_bytes": 12 * N, "TBps": 12 * N / t / 1e12, "traffic_bytes": 20 * N,
-                                   "traffic_TBps": 20 * N / t / 1e12}
-    _opt = _ops.option(_ops.OPT_SYSTEMATIC_VARIANT, 0)
-    t = timeit(lambda: ops.resample_systematic(lw, 0.3, N))
-    _opt.__exit__()
-    out["systematic_cdf_in_hbm_e2e"] = {"s": t, "alg_bytes": 12 * N, "TBps": 12 * N / t / 1e12}
-    t = timeit(lambda: ops.ess_logz(lw, None, float(N)))
-    out["ess_logz"] = {"s": t, "alg_bytes": 4 * N, "TBps": 4 * N / t / 1e12}
-    print(json.dumps(out))
+    dev = "cuda"
+    rows = []
+    for N in [int(s) for s in a.sizes.split(",")]:
+        g = torch.Generator(device=dev).manual_seed(0)
+        lw = torch.randn(N, device=dev, generator=g) * 3
+        u = torch.rand(N, device=dev, generator=g, dtype=torch.float64)
+        methods = {
+            # algorithmic bytes: log_w in, indices out (+ the uniforms in, + the uniforms written and read back)
+            "multinomial_with_rand": (lambda: ops.resample_multinomial(lw, torch.rand(N, dtype=torch.float64, device=dev)), 28 * N),
+            "multinomial": (lambda: ops.resample_multinomial(lw, u), 20 * N),
+            "systematic": (lambda: ops.resample_systematic(lw, 0.3, N), 12 * N),
+            "stream_sorted": (lambda: ops.resample_multinomial_stream(lw, 12345, N, 0), 12 * N),
+            "stream_shuffled": (lambda: ops.resample_multinomial_stream(lw, 12345, N, 1), 12 * N),
+        }
+        if a.only:
+            methods = {a.only: methods[a.only]}
+        per = max(1, a.calls // a.rounds)
+        for fn, _ in methods.values():              # warm-up: scratch of every method allocated, clocks up
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in methods}
+        for _ in range(a.rounds):                   # alternate: every method sees the same clocks / thermal state
+            for k, (fn, _) in methods.items():
+                t[k] += times(fn, per)
+        for k, (_, alg) in methods.items():
+            s = sorted(t[k])
+            med = s[len(s) // 2]
+            rows.append({"N": N, "method": k, "calls": len(s), "median_us": med * 1e6, "min_us": s[0] * 1e6, "max_us": s[-1] * 1e6,
+                         "algorithmic_bytes": alg, "GBps": alg / med / 1e9, "frac_hbm_peak": alg / med / 1e12 / PEAK_HBM_TBPS})
+            print(json.dumps(rows[-1]), flush=True)
+        del lw, u, methods
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(rows, fh, indent=1)
 
-main()
+
+if __name__ == "__main__":
+    main()
