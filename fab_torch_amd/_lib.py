@@ -114,8 +114,9 @@ SYMBOLS = [
     "fabhip_buffer_add", "fabhip_buffer_sample_workspace_bytes", "fabhip_buffer_sample",
     "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
     "fabhip_train_step_plan", "fabhip_resample_stream_workspace_bytes", "fabhip_resample_multinomial_stream",
+    "fabhip_smc_shard_workspace_bytes", "fabhip_smc_shard_pack", "fabhip_smc_shard_resample",
 ]
-ABI_VERSION = 219          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 220          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -150,6 +151,10 @@ def _declare(lib):
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]
     lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fabhip_smc_shard_workspace_bytes.restype = sz
+    lib.fabhip_smc_shard_workspace_bytes.argtypes = [i32, i64]
+    lib.fabhip_smc_shard_pack.argtypes = [C.POINTER(Point), vp, vp, i64, i32, vp, vp]
+    lib.fabhip_smc_shard_resample.argtypes = [vp, i32, i32, i64, i32, dbl, vp, C.POINTER(Point), vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fabhip_hmc_partials_floats.restype = i64
     lib.fabhip_hmc_partials_floats.argtypes = [i64]
     lib.fabhip_hmc_adapt_gathered.argtypes = [vp, i32, i64, vp, vp, C.c_float, i32, vp, vp, vp]

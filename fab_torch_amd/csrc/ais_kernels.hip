@@ -1115,6 +1115,132 @@ __global__ void k_smc_copyback(SmcGatherK a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// SMC mode over sharded chains (include/fabhip.h: fabhip_smc_shard_pack / fabhip_smc_shard_resample).  Every rank packs its
+// state into rows of RW = 3 D + 4 floats (the compaction staging's stride) + one trailer row with its live count; the host
+// all-gathers the buffers; then every rank compacts the R log-weight columns into the global live order, runs k_smc_decide on
+// them (the single-device kernel: its decision, ESS, ancestors and common log-weight are therefore the single-device bits)
+// and fetches its own rows' ancestors out of the gathered buffer.  One wave per row; with D % 4 == 0 and 16-byte aligned
+// arrays (VEC) the rows move as float4, the scalar form covers every other shape.  All kernels are always launched and read
+// the device flag / counts: the launch sequence is fixed and the host never waits.
+// ------------------------------------------------------------------------------------------------
+constexpr int SHARD_WAVES = 4;                       // rows per workgroup
+constexpr int SHARD_MAX_RANKS = 64;                  // the rank offsets are ONE wave's prefix
+
+struct SmcShardK {
+    PointDev pt;           // this rank's state [b]
+    float* log_w;          // [b]
+    const int* n_ptr;      // this rank's live count (device)
+    float* send;           // pack: [b + 1][RW] out
+    const float* gathered; // resample: [R][b + 1][RW]
+    int* offs;             // workspace [R + 1]: live rows in front of rank r; offs[R] = n0
+    int* n0;               // workspace [1]
+    float* lw_glob;        // workspace [R b]: log_w of the live rows in global order, -inf behind them
+    const int* anc;        // workspace [R b] (k_smc_decide)
+    const int* flag;
+    const float* lw_common;
+    long b;
+    int D, R, rank;
+};
+
+template <bool VEC>
+__device__ inline void shard_copy(float* __restrict__ dst, const float* __restrict__ src, int n, int lane) {
+    if (VEC) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        for (int j = lane; j < n / 4; j += 64) d4[j] = s4[j];
+    } else {
+        for (int j = lane; j < n; j += 64) dst[j] = src[j];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(64 * SHARD_WAVES) void k_smc_shard_pack(SmcShardK a) {
+    const int lane = threadIdx.x & 63, D = a.D, RW = 3 * D + 4;
+    const bool hg = a.pt.gq != nullptr;
+    const long row0 = (long)blockIdx.x * SHARD_WAVES + (threadIdx.x >> 6), stride = (long)gridDim.x * SHARD_WAVES;
+    for (long r = row0; r <= a.b; r += stride) {
+        float* o = a.send + r * RW;
+        if (r == a.b) {                                   // the trailer: this rank's live count, bit pattern of an int32
+            int n = *a.n_ptr;
+            n = n < 0 ? 0 : (n > a.b ? (int)a.b : n);
+            for (int j = lane; j < RW; j += 64) reinterpret_cast<int*>(o)[j] = j == 0 ? n : 0;
+            continue;
+        }
+        shard_copy<VEC>(o, a.pt.x + r * D, D, lane);
+        if (hg) {
+            shard_copy<VEC>(o + D, a.pt.gq + r * D, D, lane);
+            shard_copy<VEC>(o + 2 * D, a.pt.gp + r * D, D, lane);
+        }
+        if (lane < 4) o[3 * D + lane] = lane == 0 ? a.pt.lq[r] : (lane == 1 ? a.pt.lp[r] : (lane == 2 ? a.log_w[r] : 0.f));
+    }
+}
+
+// Live counts of the R trailers -> exclusive prefix (one wave, every workgroup computes it for itself), then the log-weight
+// column of every live row to its place in the global order.  Positions [n0, R b) are filled with -inf.
+__global__ __launch_bounds__(256) void k_smc_shard_prefix(SmcShardK a) {
+    __shared__ int sh_off[SHARD_MAX_RANKS + 1];
+    const int RW = 3 * a.D + 4, R = a.R;
+    if (threadIdx.x < 64) {
+        const int l = threadIdx.x;
+        int n = 0;
+        if (l < R) {
+            n = reinterpret_cast<const int*>(a.gathered)[((long)l * (a.b + 1) + a.b) * RW];
+            n = n < 0 ? 0 : (n > a.b ? (int)a.b : n);
+        }
+        int inc = n;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(inc, off);
+            if (l >= off) inc += t;
+        }
+        if (l < R) sh_off[l + 1] = inc;
+        if (l == 0) sh_off[0] = 0;
+    }
+    __syncthreads();
+    const long cap = (long)R * a.b;
+    const int n0 = sh_off[R];
+    if (blockIdx.x == 0) {
+        for (int l = threadIdx.x; l <= R; l += blockDim.x) a.offs[l] = sh_off[l];
+        if (threadIdx.x == 0) *a.n0 = n0;
+    }
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < cap; g += (long)gridDim.x * blockDim.x) {
+        const int s = (int)(g / a.b);
+        const long i = g - (long)s * a.b;
+        if (i < sh_off[s + 1] - sh_off[s]) a.lw_glob[sh_off[s] + i] = a.gathered[((long)s * (a.b + 1) + i) * RW + 3 * a.D + 2];
+        if (g >= n0) a.lw_glob[g] = -INFINITY;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(64 * SHARD_WAVES) void k_smc_shard_gather(SmcShardK a) {
+    if (*a.flag == 0) return;
+    const int lane = threadIdx.x & 63, D = a.D, RW = 3 * D + 4, R = a.R;
+    const bool hg = a.pt.gq != nullptr;
+    long nr = *a.n_ptr;
+    nr = nr < 0 ? 0 : (nr > a.b ? a.b : nr);
+    const int n0 = a.offs[R], off_r = a.offs[a.rank];
+    const int end_l = lane < R ? a.offs[lane + 1] : 0x7fffffff;       // lane s: one past the last global row of rank s
+    const float lw = *a.lw_common;
+    const long row0 = (long)blockIdx.x * SHARD_WAVES + (threadIdx.x >> 6), stride = (long)gridDim.x * SHARD_WAVES;
+    for (long i = row0; i < nr; i += stride) {
+        if (off_r + i >= n0) break;                        // (a trailer that disagrees with n_valid: nothing to fetch)
+        int g = a.anc[off_r + i];
+        g = g < 0 ? 0 : (g >= n0 ? n0 - 1 : g);
+        // source rank = the ranks whose rows all lie in front of g (the offsets are monotone; empty ranks count themselves out)
+        int s = __popcll(__ballot(end_l <= g));
+        s = s > R - 1 ? R - 1 : s;
+        long row = g - a.offs[s];
+        row = row < 0 ? 0 : (row >= a.b ? a.b - 1 : row);
+        const float* src = a.gathered + ((long)s * (a.b + 1) + row) * RW;
+        shard_copy<VEC>(a.pt.x + i * D, src, D, lane);
+        if (hg) {
+            shard_copy<VEC>(a.pt.gq + i * D, src + D, D, lane);
+            shard_copy<VEC>(a.pt.gp + i * D, src + 2 * D, D, lane);
+        }
+        if (lane == 0) { a.pt.lq[i] = src[3 * D]; a.pt.lp[i] = src[3 * D + 1]; a.log_w[i] = lw; }
+    }
+}
+
 __global__ void k_sub(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = a[i] - b[i];
 }
@@ -1892,6 +2018,77 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
     if (do_finish)
         FAB_TRY(phase_tail(a->point, a->log_w, B, D, a->n_valid, a->n_valid + 1, tmp, dest, nullptr, nullptr, (double)B,
                            a->stats + 3, ess_ws, ess_bytes, nullptr, nullptr, nullptr, st));
+    return check_launch();
+}
+
+// ---- SMC mode over sharded chains -------------------------------------------------------------------------------------------
+static inline bool shard_vec_ok(const fabhip_point& p, const float* buf, int D) {
+    auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
+    return D % 4 == 0 && al(buf) && al(p.x) && (!p.grad_log_q || (al(p.grad_log_q) && al(p.grad_log_p)));
+}
+static inline int shard_grid(long rows) {
+    const long g = (rows + SHARD_WAVES - 1) / SHARD_WAVES;
+    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+}
+
+size_t fabhip_smc_shard_workspace_bytes(int32_t R, int64_t b) {
+    if (R < 1 || R > SHARD_MAX_RANKS || b < 1) return 0;
+    const size_t cap = (size_t)R * (size_t)b;
+    // offsets [R + 1] + n0 | flag, common log-weight | global log_w | CDF | ancestors
+    return 512 + 256 + align256(cap * 4) + align256(cap * 8) + align256(cap * 4);
+}
+
+int fabhip_smc_shard_pack(const fabhip_point* point, const float* log_w, const int32_t* n_valid, int64_t b, int32_t dim,
+                          float* send, fabhip_stream_t stream) {
+    if (!point || !point->x || !point->log_q || !point->log_p || !log_w || !n_valid || !send) return FABHIP_EINVAL;
+    if ((point->grad_log_q == nullptr) != (point->grad_log_p == nullptr)) return FABHIP_EINVAL;
+    if (b < 1 || b > 0x3fffffffL || dim < 1 || dim > FABHIP_MAX_DIM) return FABHIP_EINVAL;
+    SmcShardK k{};
+    k.pt = make_point_dev(*point); k.log_w = const_cast<float*>(log_w); k.n_ptr = n_valid; k.send = send;
+    k.b = (long)b; k.D = dim; k.R = 1; k.rank = 0;
+    const int grid = shard_grid((long)b + 1);
+    if (shard_vec_ok(*point, send, dim)) hipLaunchKernelGGL(k_smc_shard_pack<true>, dim3(grid), dim3(64 * SHARD_WAVES), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL(k_smc_shard_pack<false>, dim3(grid), dim3(64 * SHARD_WAVES), 0, (hipStream_t)stream, k);
+    return check_launch();
+}
+
+int fabhip_smc_shard_resample(const float* gathered, int32_t R, int32_t rank, int64_t b, int32_t dim, double tau, const double* u,
+                              const fabhip_point* point, float* log_w, const int32_t* n_valid, int32_t* resampled, float* ess,
+                              int32_t* ancestors, float* log_w_pre, void* workspace, size_t workspace_bytes,
+                              fabhip_stream_t stream) {
+    if (!gathered || !u || !point || !point->x || !point->log_q || !point->log_p || !log_w || !n_valid || !workspace)
+        return FABHIP_EINVAL;
+    if ((point->grad_log_q == nullptr) != (point->grad_log_p == nullptr)) return FABHIP_EINVAL;
+    if (R < 1 || rank < 0 || rank >= R || b < 1 || dim < 1 || dim > FABHIP_MAX_DIM) return FABHIP_EINVAL;
+    if (R > SHARD_MAX_RANKS) return FABHIP_ENOTSUP;
+    if ((int64_t)R * b > 0x3fffffffL) return FABHIP_EINVAL;
+    if (((size_t)workspace & 255) != 0) return FABHIP_EINVAL;
+    if (workspace_bytes < fabhip_smc_shard_workspace_bytes(R, b)) return FABHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const long cap = (long)R * (long)b;
+    char* p = (char*)workspace;
+    int* offs = (int*)p; int* n0 = (int*)(p + 448); p += 512;
+    int* flag = (int*)p; float* common = (float*)(p + 64); p += 256;
+    float* lw_glob = (float*)p; p += align256((size_t)cap * 4);
+    unsigned long long* cdf = (unsigned long long*)p; p += align256((size_t)cap * 8);
+    int* anc = (int*)p;
+    SmcShardK k{};
+    k.pt = make_point_dev(*point); k.log_w = log_w; k.n_ptr = n_valid; k.gathered = gathered;
+    k.offs = offs; k.n0 = n0; k.lw_glob = lw_glob; k.anc = anc; k.flag = flag; k.lw_common = common;
+    k.b = (long)b; k.D = dim; k.R = R; k.rank = rank;
+    // 1. counts -> offsets, the global log-weight column
+    const long pg = (cap + 255) / 256;
+    hipLaunchKernelGGL(k_smc_shard_prefix, dim3((unsigned)(pg > 1024 ? 1024 : pg)), dim3(256), 0, st, k);
+    // 2. the single-device decision on it
+    SmcK d;
+    d.log_w = lw_glob; d.n_ptr = n0; d.B = cap; d.tau = tau; d.u = u;
+    d.cdf = cdf; d.anc = anc; d.flag = flag; d.lw_common = common;
+    d.resampled_out = resampled; d.ess_out = ess; d.anc_out = ancestors; d.lw_pre_out = log_w_pre;
+    FAB_TRY(smc_decide(d, st));
+    // 3. this rank's rows fetch their ancestors
+    const int grid = shard_grid((long)b);
+    if (shard_vec_ok(*point, gathered, dim)) hipLaunchKernelGGL(k_smc_shard_gather<true>, dim3(grid), dim3(64 * SHARD_WAVES), 0, st, k);
+    else hipLaunchKernelGGL(k_smc_shard_gather<false>, dim3(grid), dim3(64 * SHARD_WAVES), 0, st, k);
     return check_launch();
 }
 

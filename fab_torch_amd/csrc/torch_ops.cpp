@@ -1200,6 +1200,55 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, doubl
     return {anc.to(at::kLong), flag, ess, common};
 }
 
+// SMC mode over sharded chains (fabhip_smc_shard_pack / fabhip_smc_shard_resample; fab_torch_amd/parallel.py steps the loop).
+// pack: this rank's send buffer [b + 1, 3 D + 4] (row b: its live count, read from n_valid on the device).
+static fabhip_point shard_point(const Tensor& x, const Tensor& log_q, const Tensor& log_p, const optional<Tensor>& gq,
+                                const optional<Tensor>& gp) {
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "fabhip: x must be [b, D] with b >= 1");
+    TORCH_CHECK(gq.has_value() == gp.has_value(), "fabhip: grad_log_q and grad_log_p come together");
+    const int64_t b = x.size(0), D = x.size(1);
+    return fabhip_point{fpm(x, "x"), fpmn(log_q, b, x, "log_q"), fpmn(log_p, b, x, "log_p"),
+                        fpmn_opt(gq, b * D, x, "grad_log_q"), fpmn_opt(gp, b * D, x, "grad_log_p")};
+}
+
+Tensor smc_shard_pack(const Tensor& x, const Tensor& log_q, const Tensor& log_p, const optional<Tensor>& grad_log_q,
+                      const optional<Tensor>& grad_log_p, const Tensor& log_w, const Tensor& n_valid) {
+    c10::DeviceGuard g(x.device());
+    const fabhip_point pt = shard_point(x, log_q, log_p, grad_log_q, grad_log_p);
+    const int64_t b = x.size(0), D = x.size(1);
+    need(n_valid, at::kInt, "n_valid"); need_n(n_valid, 1, x, "n_valid", true);
+    Tensor send = fempty({b + 1, 3 * D + 4}, x);
+    chk(fabhip_smc_shard_pack(&pt, fpn(log_w, b, x, "log_w"), n_valid.data_ptr<int32_t>(), b, (int32_t)D,
+                              send.data_ptr<float>(), stream_of(x)), "smc_shard_pack");
+    return send;
+}
+
+// resample: the state tensors in place; (resampled int32[1], ess float[1], ancestors int32[R b], log_w_pre float[R b]) - the
+// last two empty unless want_trace.
+std::tuple<Tensor, Tensor, Tensor, Tensor> smc_shard_resample(
+    const Tensor& gathered, int64_t world, int64_t rank, double tau, const Tensor& u, Tensor x, Tensor log_q, Tensor log_p,
+    optional<Tensor> grad_log_q, optional<Tensor> grad_log_p, Tensor log_w, const Tensor& n_valid, bool want_trace) {
+    c10::DeviceGuard g(x.device());
+    const fabhip_point pt = shard_point(x, log_q, log_p, grad_log_q, grad_log_p);
+    const int64_t b = x.size(0), D = x.size(1);
+    TORCH_CHECK(world >= 1 && rank >= 0 && rank < world, "fabhip: smc_shard_resample needs 0 <= rank < world");
+    need(u, at::kDouble, "u");
+    TORCH_CHECK(u.numel() == 1 && u.device() == x.device(), "fabhip: u must be ONE float64 on the state's device");
+    need(n_valid, at::kInt, "n_valid"); need_n(n_valid, 1, x, "n_valid", true);
+    const float* gat = fpn(gathered, world * (b + 1) * (3 * D + 4), x, "gathered");
+    Tensor flag = at::empty({1}, x.options().dtype(at::kInt)), ess = fempty({1}, x);
+    Tensor anc = at::empty({want_trace ? world * b : 0}, x.options().dtype(at::kInt));
+    Tensor pre = fempty({want_trace ? world * b : 0}, x);
+    const size_t nb = fabhip_smc_shard_workspace_bytes((int32_t)world, b);
+    Tensor ws = scratch(nb, x);
+    chk(fabhip_smc_shard_resample(gat, (int32_t)world, (int32_t)rank, b, (int32_t)D, tau, u.data_ptr<double>(), &pt,
+                                  fpmn(log_w, b, x, "log_w"), n_valid.data_ptr<int32_t>(), flag.data_ptr<int32_t>(),
+                                  ess.data_ptr<float>(), want_trace ? anc.data_ptr<int32_t>() : nullptr,
+                                  want_trace ? pre.data_ptr<float>() : nullptr, aligned(ws), nb, stream_of(x)),
+        "smc_shard_resample");
+    return {flag, ess, anc, pre};
+}
+
 // One shard's WHOLE tuned AIS call in one op: chain initialisation, M x {HMC transition publishing its
 // acceptance slab, ONE all-gather of the slabs through the c10d process group registered as `group_name` (RCCL over xGMI
 // on a GPU node), the step-size rule of hmc.py:162-170 on the joined slabs in rank order (fabhip_hmc_adapt_gathered: every
@@ -1489,6 +1538,11 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor(q!)? base_log_w, int precision, float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
           "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre) -> ()");
     m.def("smc_decide(Tensor log_w, float tau, Tensor u) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("smc_shard_pack(Tensor x, Tensor log_q, Tensor log_p, Tensor? grad_log_q, Tensor? grad_log_p, Tensor log_w, "
+          "Tensor n_valid) -> Tensor");
+    m.def("smc_shard_resample(Tensor gathered, int world, int rank, float tau, Tensor u, Tensor(a!) x, Tensor(b!) log_q, "
+          "Tensor(c!) log_p, Tensor(d!)? grad_log_q, Tensor(e!)? grad_log_p, Tensor(f!) log_w, Tensor n_valid, "
+          "bool want_trace) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("ais_sharded_tuned(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor? eps0, "
           "Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int L, "
           "float max_grad, float target_p_accept, Tensor(c!) x, Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, "
@@ -1570,6 +1624,8 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("ais_run_smc", ais_run_smc);
     m.impl("ais_phase_smc", ais_phase_smc);
     m.impl("smc_decide", smc_decide);
+    m.impl("smc_shard_pack", smc_shard_pack);
+    m.impl("smc_shard_resample", smc_shard_resample);
     m.impl("ais_sharded_tuned", ais_sharded_tuned);
     m.impl("metropolis_adapt_gathered", metropolis_adapt_gathered);
     m.impl("tape_gemm", tape_gemm);

@@ -78,6 +78,20 @@ def all_gather_rows(buf: torch.Tensor, group=None) -> torch.Tensor:
     return out
 
 
+def broadcast_from_rank0(t: torch.Tensor, group=None) -> torch.Tensor:
+    """`t` of rank 0 on every rank (in place): ONE broadcast, fed through the host where the backend is host-only."""
+    if _world(group) == 1:
+        return t
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    if t.is_cuda and dist.get_backend(group) != "nccl":
+        host = t.cpu().contiguous()
+        dist.broadcast(host, src, group=group)
+        t.copy_(host)
+    else:
+        dist.broadcast(t, src, group=group)
+    return t
+
+
 def gather_particles(x, log_w, log_q, capacity: int, group=None, compact: bool = True):
     """All-gather fixed-size shards (invalid rows stay in place with log_w = -inf, compaction after).
     compact=False skips the compaction - and with it the host synchronisation of the boolean-mask indexing: the result
@@ -96,7 +110,8 @@ def refuse_resampling(who: str, threshold):
     if threshold is not None:
         from ._ops import FabhipError
         raise FabhipError(f"{who}: resample_threshold={threshold} (SMC mode) is not available for sharded chains; "
-                          "set resample_threshold=None on the sampler")
+                          "set resample_threshold=None on the sampler (ShardedAnnealedImportanceSampler resamples over all "
+                          "ranks when it is built with resample_across_ranks=True)")
 
 
 class ShardedAIS:
@@ -193,12 +208,13 @@ class HipShardBackend:
         op = self.op
         self.ops.metropolis_adapt_gathered(gathered, int(world), int(b), op.noise_scalings, float(op.target_prob_accept), True)
 
-    def run_fused(self, b, eps0=None, noise_a=None, noise_b=None):
+    def run_fused(self, b, eps0=None, noise_a=None, noise_b=None, noise_r=None):
         from .ais import NoValidPoints
         from .point import Point
         self.empty_phase = None
+        smc = {} if noise_r is None else {"noise_r": noise_r}         # (the uniforms of the rank-local fused SMC call)
         try:
-            pt, log_w = self.ais.sample_and_log_weights(b, eps0=eps0, noise_a=noise_a, noise_b=noise_b)
+            pt, log_w = self.ais.sample_and_log_weights(b, eps0=eps0, noise_a=noise_a, noise_b=noise_b, **smc)
         except NoValidPoints as e:                        # the reference's "No valid points ..." (ais.py:201,211) of THIS shard,
             self.empty_phase = e.phase                    # and nothing else (the message text of any Exception was matched)
             # an empty shard - the gathered set decides (see finish).  The shape of an empty Point comes from the sampler's own
@@ -287,10 +303,29 @@ class HipShardBackend:
               "slab": torch.empty(int(self.ops.hmc_partials_floats(int(b))), **f32)}
         return st
 
-    def step(self, st, j) -> torch.Tensor:
-        """Transition j with the adaptation deferred: returns this rank's acceptance slab."""
+    def step(self, st, j, tune: bool = True) -> torch.Tensor:
+        """Transition j with the adaptation deferred: returns this rank's acceptance slab.  `tune=False` (tuning frozen, the
+        stepped loop of the SMC mode): the plain transition, nothing is published."""
+        if not tune:
+            self._phase(st, 0, j, j, partials=None, tune=False)
+            return None
         self._phase(st, 0, j, j, partials=st["slab"], tune=True)
         return st["slab"]
+
+    @property
+    def device(self):
+        return self.ais._native_parts()[0]._nf_model.q0.loc.device
+
+    def pack(self, st) -> torch.Tensor:
+        """This rank's send buffer of the state gather, [b + 1, 3 D + 4] (fabhip_smc_shard_pack: one launch; row b carries the
+        live count, read on the device)."""
+        return self.ops.smc_shard_pack(st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"])
+
+    def resample(self, st, j, gathered, world, rank, u_j, trace: bool = False):
+        """The resampling step in front of transition j on the gathered state of all ranks (fabhip_smc_shard_resample: three
+        launches whatever the decision).  Returns device tensors (resampled [1], ess [1], ancestors, log_w_pre)."""
+        return self.ops.smc_shard_resample(gathered, int(world), int(rank), float(self.ais.resample_threshold), u_j, st["x"],
+                                           st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], bool(trace))
 
     def adapt(self, st, j, gathered, world):
         op, M = self.op, self.n_transitions
@@ -327,11 +362,28 @@ class ShardedAnnealedImportanceSampler:
     of its chains is an empty shard, not an error: "No valid points" is raised - on every rank - only when the GATHERED set is
     empty (compact=True; with compact=False `logging_info` shows it).  Bit-for-bit equality with one device holds when both
     use the same tile shape (`FABHIP_OPT_TILE_SHAPE`, or batches that select the same one: chains per workgroup follow the
-    LOCAL batch)."""
+    LOCAL batch).
 
-    def __init__(self, ais=None, group=None, backend=None, one_op: Optional[bool] = None):
+    `resample_across_ranks=True` (opt-in; the default refuses a sampler with `resample_threshold` set): the SMC mode over ALL
+    chains.  Before every transition the ranks all-gather their state ([b + 1, 3 D + 4] floats per rank: point, log-weight
+    and live count), every rank takes the single-device decision (the same kernel on the log-weights of all live chains, one
+    uniform shared by all ranks) and fetches the ancestors of its own rows out of the gathered set - bit for bit the
+    single-device SMC run under the conditions above when chains have only dropped in the last non-empty shard (every
+    rank's live rows then start at global row rank * b, the noise row one device would use).  HMC with n_outer == 1 over a
+    RealNVP flow and a native target; the loop is stepped from Python (the one-op C++ loop has no resampling step) and
+    Metropolis is refused.  `n_state_gathers` counts the state gathers of the last call, `last_smc` holds
+    (resampled [M], ess [M], ancestors, log_w_pre) - the last two per transition over the global live order with
+    `trace=True`, empty otherwise."""
+
+    def __init__(self, ais=None, group=None, backend=None, one_op: Optional[bool] = None,
+                 resample_across_ranks: bool = False):
         import os
         self.group = group
+        self.resample_across_ranks = bool(resample_across_ranks)
+        self.n_state_gathers = 0                # state all-gathers (SMC mode over ranks) issued by the last call
+        self.last_smc = None
+        self.last_noise_r = None                # the uniforms the last call's resampling steps used (the same on all ranks)
+        self._warned_stepped = False
         self.backend = backend if backend is not None else HipShardBackend(ais)
         # tuned calls: one op per call (default) or the Python-stepped loop it replaced (FABHIP_SHARDED_ONE_OP=0: kept as
         # the reference implementation - tests/test_gpu_sharded.py compares the two bit for bit)
@@ -363,14 +415,73 @@ class ShardedAnnealedImportanceSampler:
                              "(the acceptance slabs of all ranks must have one shape); set_eval_mode(True) takes uneven splits")
         return shard_sizes(total_batch, world)[_rank(self.group)]
 
+    def _uniforms(self, noise_r, device):
+        """The M uniforms of the call's resampling steps, the same on every rank: the caller's, or rank 0's draw broadcast once."""
+        from .ais import check_noise_r
+        M = self.backend.n_transitions
+        if noise_r is not None:
+            return check_noise_r(noise_r, M)
+        u = torch.rand(M, dtype=torch.float64, device=device) if _rank(self.group) == 0 \
+            else torch.empty(M, dtype=torch.float64, device=device)
+        return broadcast_from_rank0(u, self.group)
+
+    def _run_smc_stepped(self, b, world, eps0, noise_a, noise_b, noise_r, trace):
+        """begin / M x (pack, state all-gather, resample, step [, slab all-gather, adapt]) / finish.  The state gather is issued
+        every transition whatever the decision: nothing in the loop reads the device."""
+        be, rank = self.backend, _rank(self.group)
+        tuning = bool(be.tuning)
+        st = be.begin(b, eps0, noise_a, noise_b)
+        record = []
+        for j in range(1, be.n_transitions + 1):
+            gathered = all_gather_rows(be.pack(st), self.group)
+            self.n_state_gathers += 1
+            record.append(be.resample(st, j, gathered, world, rank, noise_r[j - 1:j], trace=trace))
+            slab = be.step(st, j, tune=tuning)
+            if tuning:
+                be.adapt(st, j, all_gather_rows(slab.reshape(1, -1), self.group).reshape(-1), world)
+                self.n_slab_gathers += 1
+        self.last_smc = (torch.cat([r[0].reshape(-1) for r in record]), torch.cat([r[1].reshape(-1) for r in record]),
+                         torch.stack([r[2] for r in record]), torch.stack([r[3] for r in record]))
+        return be.finish(st)
+
     def sample_and_log_weights(self, total_batch: int, eps0=None, noise_a=None, noise_b=None, compact: bool = True,
-                               logging: bool = True):
+                               logging: bool = True, noise_r=None, trace: bool = False):
         world = _world(self.group)
         be = self.backend
-        refuse_resampling("ShardedAnnealedImportanceSampler", getattr(getattr(be, "ais", None), "resample_threshold", None))
+        tau = getattr(getattr(be, "ais", None), "resample_threshold", None)
+        smc_on = self.resample_across_ranks and tau is not None
+        if not self.resample_across_ranks:
+            refuse_resampling("ShardedAnnealedImportanceSampler", tau)
+        if noise_r is not None and not smc_on:
+            from ._ops import FabhipError
+            raise FabhipError("noise_r belongs to the SMC mode over ranks: resample_across_ranks=True and a sampler with "
+                              "resample_threshold set")
         b = self.local_batch(total_batch)
-        self.n_slab_gathers = 0
-        if world == 1 or not be.tuning:
+        self.n_slab_gathers = self.n_state_gathers = 0
+        self.last_smc = self.last_noise_r = None
+        if smc_on:
+            from ._ops import FabhipError
+            if not getattr(be, "hmc", True):
+                raise FabhipError("ShardedAnnealedImportanceSampler: resample_across_ranks with Metropolis transitions is not "
+                                  "available (the deferred noise-scaling rule runs the whole call in one piece); use HMC")
+            if total_batch % world:
+                raise ValueError(f"resample_across_ranks: {total_batch} chains do not split evenly over {world} ranks (the "
+                                 "state buffers of all ranks must have one shape)")
+        if smc_on and world > 1:
+            if self.one_op and hasattr(be, "run_tuned") and be.tuning and not self._warned_stepped:
+                import warnings
+                self._warned_stepped = True
+                warnings.warn("fab_torch_amd: resample_across_ranks - the one-op C++ loop (ais_sharded_tuned) has no resampling "
+                              "step; the Python-stepped loop is used (same values)")
+            self.last_noise_r = noise_r = self._uniforms(noise_r, getattr(be, "device", "cpu"))
+            pt, log_w = self._run_smc_stepped(b, world, eps0, noise_a, noise_b, noise_r, trace)
+        elif smc_on:                                       # one rank: the fused SMC call, no collective
+            if noise_r is not None:
+                from .ais import check_noise_r
+                self.last_noise_r = noise_r = check_noise_r(noise_r, be.n_transitions)
+            pt, log_w = be.run_fused(b, eps0, noise_a, noise_b, noise_r=noise_r)
+            self.last_smc = getattr(getattr(be, "ais", None), "last_smc", None)
+        elif world == 1 or not be.tuning:
             pt, log_w = be.run_fused(b, eps0, noise_a, noise_b)
         elif not getattr(be, "hmc", True):                 # Metropolis: the whole call, then ONE slab gather + the rule
             pt, log_w, slab = be.run_metropolis_deferred(b, eps0, noise_a, noise_b)
@@ -402,6 +513,9 @@ class ShardedAnnealedImportanceSampler:
             x, lw, lq = buf[:, :D], buf[:, D], buf[:, D + 1]
         if logging:
             self.logging_info = self._global_stats(lw, total_batch, n_valid)
+            if smc_on and self.last_smc is not None:       # device scalars, like the rest: no synchronisation
+                self.logging_info["n_resampled"] = self.last_smc[0].sum()
+                self.logging_info["ess_min_in_chain"] = self.last_smc[1].min()
         return x, lw, lq
 
     @staticmethod

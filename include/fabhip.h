@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 219
+#define FABHIP_ABI_VERSION 220
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -643,6 +643,31 @@ size_t fabhip_smc_workspace_bytes(int64_t B);
 int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
                       int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
                       size_t workspace_bytes, fabhip_stream_t stream);
+
+/* SMC mode over SHARDED chains (fab_torch_amd/parallel.py: resample_across_ranks; definition: tests/smc_shard_spec.py).
+ * R ranks hold b rows each, the first n_r = n_valid[0] of them live; the global live order is the ranks' live rows in rank
+ * order, n0 = sum n_r, off_r = sum_{s<r} n_s.  Before a transition every rank packs its state, the host all-gathers the R
+ * buffers, and every rank runs the resampling step on the gathered set: the decision is fabhip_smc_decide's kernel on the
+ * n0 global log-weights (its decision, ess, ancestors and common log-weight are the single-device call's bits), and local
+ * row i < n_r becomes global row ancestors[off_r + i].  Counts do not change; rows at and beyond n_r are untouched.
+ *
+ * fabhip_smc_shard_pack: ONE launch writes send [b + 1][RW], RW = 3 dim + 4: row i < b = x | grad log q | grad log p |
+ * log q, log p, log w, 0 (the gradient slots are left unwritten when point->grad_log_q == NULL), row b = n_r (an int32 bit
+ * pattern in its first word, read from the device's n_valid[0]; the rest 0). */
+int fabhip_smc_shard_pack(const fabhip_point* point, const float* log_w, const int32_t* n_valid, int64_t b, int32_t dim,
+                          float* send, fabhip_stream_t stream);
+/* fabhip_smc_shard_resample: gathered [R][b + 1][RW] (the R send buffers in rank order), this rank's state in / out.  Three
+ * launches whatever the decision (the kernels read the device flag; the host never waits): counts -> offsets and the global
+ * log-weight column, the decision, the fetch of this rank's ancestors out of `gathered` (one wave per row; 16-byte accesses
+ * when dim % 4 == 0 and the arrays are 16-byte aligned).  u: device, one double.  Outputs, each may be NULL: resampled [1],
+ * ess [1], ancestors [R b] (global live indices; the identity where nothing is resampled and beyond n0), log_w_pre [R b]
+ * (the n0 global log-weights the decision saw, -inf behind them).  R > 64: FABHIP_ENOTSUP (the offsets are one wave's
+ * prefix).  workspace: 256-byte aligned, fabhip_smc_shard_workspace_bytes(R, b) (0 for an unsupported R). */
+size_t fabhip_smc_shard_workspace_bytes(int32_t R, int64_t b);
+int fabhip_smc_shard_resample(const float* gathered, int32_t R, int32_t rank, int64_t b, int32_t dim, double tau, const double* u,
+                              const fabhip_point* point, float* log_w, const int32_t* n_valid, int32_t* resampled, float* ess,
+                              int32_t* ancestors, float* log_w_pre, void* workspace, size_t workspace_bytes,
+                              fabhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same with the RQ-spline flow (fabhip_spline_*) as base distribution

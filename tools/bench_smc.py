@@ -7,7 +7,11 @@ Timing: ms per `sample_and_log_weights` call (wall clock over CALLS calls, REPEA
   tau=0          the decision runs before every transition and never fires,
   tau=1.5        it fires every time (gather + copy-back move the whole point).
 log Z: error of the call's log_Z against the target's exact normaliser (AIS target p, tuning off, step 0.1) over SEEDS seeds for
-off and tau = 0.5, with the untrained seeded flow of the benchmark.  One JSON line."""
+off and tau = 0.5, with the untrained seeded flow of the benchmark.
+Resampling step alone (HIP events around CALLS steps, REPEATS repeats, us per step): the sharded step - smc_shard_pack +
+smc_shard_resample on an emulated gathered buffer of 8 ranks x 2048 chains (the collective itself is NOT in it) - next to the
+single-device step (decision + gather + copy-back, ais_phase_smc with only_resample) at 2048 and at 16384 chains, each firing
+(tau = 1.5) and not firing (tau = 0).  One JSON line."""
 import json
 import os
 import sys
@@ -64,6 +68,56 @@ def log_z_errors(B, tau):
             "of_steps": SEEDS * M}
 
 
+def _event_us(fn):
+    """us per call of `fn`: CALLS calls between two HIP events, REPEATS repeats (median, min, max) after a warm-up."""
+    for _ in range(100):
+        fn()
+    us = []
+    for _ in range(REPEATS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(CALLS):
+            fn()
+        e1.record(); e1.synchronize()
+        us.append(e0.elapsed_time(e1) / CALLS * 1e3)
+    us.sort()
+    return {"us_median": us[len(us) // 2], "us_min": us[0], "us_max": us[-1]}
+
+
+def _phase_state(B, tau):
+    """A sampler's state after FABHIP_AIS_INIT, stepped through the phase op (the sharded backend's own state tensors)."""
+    from fab_torch_amd import parallel
+    ais = sampler(tau, tune=False)
+    be = parallel.HipShardBackend(ais)
+    torch.manual_seed(2)
+    return ais, be, be.begin(B)
+
+
+def single_device_step(B, tau):
+    from fab_torch_amd import _ops
+    ais, be, st = _phase_state(B, tau)
+    op, ops = be.op, be.ops
+    nr = torch.rand(M, dtype=torch.float64, device=DEV)
+    args = (*be._common(st), 0, 1, 1, st["eps0"], st["noise_a"], st["noise_b"], op.epsilons, op.common_epsilon, op.mass_vector, 1,
+            op.L, float(op.max_grad), float(op.target_p_accept), False, st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"],
+            st["n_valid"], st["stats"], None, None, None, None, None, None, None, _ops.precision_of(flow), float(tau), nr, True,
+            None, None, None, None)
+    return _event_us(lambda: ops.ais_phase_smc(*args))
+
+
+def sharded_step(R, b, tau):
+    """pack + resample of rank 0 on a gathered buffer made of R copies of its own send buffer (with their own log-weights)."""
+    ais, be, st = _phase_state(b, tau)
+    u = torch.rand(1, dtype=torch.float64, device=DEV)
+    gathered = be.pack(st).repeat(R, 1)
+    gathered.view(R, b + 1, -1)[:, :b, 3 * D + 2] += torch.randn(R, b, device=DEV)
+
+    def step():
+        be.pack(st)
+        be.resample(st, 1, gathered, R, 0, u)
+    return _event_us(step)
+
+
 out = {"config": f"ManyWell-{D}, RealNVP 10x(16-320-320-32), M={M}, HMC L={L}", "lib_srchash": _lib_srchash()[:12],
        "calls": CALLS, "repeats": REPEATS}
 for B in (1024, 2048):
@@ -74,4 +128,8 @@ for B in (1024, 2048):
     row["us_per_transition_tau_1.5"] = (row["tau_1.5"]["ms_median"] - base) / M * 1e3
     out[f"B{B}"] = row
 out["log_Z_error_B1024"] = {"off": log_z_errors(1024, None), "tau_0.5": log_z_errors(1024, 0.5)}
+out["resampling_step_us"] = {
+    f"tau_{tau}": {"sharded_R8_b2048": sharded_step(8, 2048, tau), "single_B2048": single_device_step(2048, tau),
+                   "single_B16384": single_device_step(16384, tau)} for tau in (1.5, 0.0)}
+out["resampling_step_us"]["state_payload_bytes_per_rank"] = {"sent": (2048 + 1) * (3 * D + 4) * 4, "received": 8 * (2048 + 1) * (3 * D + 4) * 4}
 print(json.dumps(out))
