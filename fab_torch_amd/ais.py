@@ -4,6 +4,7 @@
 initial log-weights, NaN/inf compaction, M fused transitions with log-weight accumulation, final
 compaction and ESS / log Z — enqueued back-to-back on the current HIP stream with a single small
 device->host read at the end (row counts + logging scalars)."""
+from collections import namedtuple
 from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -40,6 +41,25 @@ def check_noise_r(noise_r: torch.Tensor, M: int) -> torch.Tensor:
         got = (tuple(noise_r.shape), noise_r.dtype) if torch.is_tensor(noise_r) else type(noise_r).__name__
         raise _ops.FabhipError(f"noise_r must be a float64 tensor of shape [{int(M)}] (one uniform per transition), got {got}")
     return noise_r.contiguous()
+
+
+# The transition operator's segment of the fused ops' argument lists, in schema order (ais_run / ais_run_smc / spline_ais_run
+# take it whole; ais_phase takes the four logging slots apart, behind the state tensors).
+OperatorSlots = namedtuple("OperatorSlots", "step_state common_epsilon mass n_inner L max_grad target_p_accept tune "
+                                            "p_accept_first p_accept_last avg_distance_first avg_distance_last")
+
+
+def operator_slots(op) -> Tuple[int, OperatorSlots]:
+    """(transition kind, the operator's slots) of this package's HMC / Metropolis."""
+    if isinstance(op, HamiltonianMonteCarlo):
+        return _ops.TRANSITION_HMC, OperatorSlots(
+            op.epsilons, op.common_epsilon, op.mass_vector, op.n_outer, op.L, float(op.max_grad), float(op.target_p_accept),
+            not op.eval_mode, op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last)
+    if isinstance(op, Metropolis):
+        return _ops.TRANSITION_METROPOLIS, OperatorSlots(
+            op.noise_scalings, None, None, op.n_updates, 0, 0.0, float(op.target_prob_accept),
+            bool(op.adjust_step_size and not op.eval_mode), None, None, None, None)
+    raise _ops.FabhipError("transition_operator must be a fab_torch_amd HamiltonianMonteCarlo / Metropolis")
 
 
 def _check_threshold(tau):
@@ -133,11 +153,9 @@ class AnnealedImportanceSampler:
         """`run` for the spline family: ONE op call (torch.ops.fabhip.spline_ais_run).  `eps0` / `u0` [B, D]: the normal /
         uniform draws of the flow's base sample."""
         self._refuse_resampling("the fused spline-flow call")
-        ops = _ops.load()
         flow, target = self._spline_parts()
         op = self.transition_operator
-        if bool(op.p_target) != bool(self.p_target) or (not self.p_target and op.alpha != self.alpha):
-            raise _ops.FabhipError("AIS and transition operator disagree on p_target / alpha")
+        head = self._call_head(flow, target, _ops.TRANSITION_HMC)[:-1]       # (HMC only: the spline op has no transition slot)
         dev = flow._tail_bound.device
         B, D, M = int(batch_size), flow.dim, self.n_intermediate_distributions
         f32 = dict(dtype=torch.float32, device=dev)
@@ -145,12 +163,8 @@ class AnnealedImportanceSampler:
         eps0 = torch.randn((B, D), **f32) if eps0 is None else eps0.contiguous()
         noise_a = torch.randn((M, op.n_outer, B, D), **f32) if noise_a is None else noise_a.contiguous()
         noise_b = torch.empty((M, op.n_outer, B), **f32).exponential_(1.0) if noise_b is None else noise_b.contiguous()
-        alpha = float(self.alpha) if self.alpha is not None else 0.0
-        out = ops.spline_ais_run(*flow.native(), *target.native_target(), self._betas(), alpha,
-                                 bool(self.p_target), u0, eps0, noise_a, noise_b, op.epsilons, op.common_epsilon,
-                                 op.mass_vector, op.n_outer, op.L, float(op.max_grad), float(op.target_p_accept),
-                                 not op.eval_mode, op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last,
-                                 bool(want_base), _ops.precision_of(flow))
+        out = _ops.load().spline_ais_run(*head, u0, eps0, noise_a, noise_b, *operator_slots(op)[1], bool(want_base),
+                                         _ops.precision_of(flow))
         x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw = out
         return Point(x, lq, lp, gq, gp), log_w, n_valid, stats, base_x, base_lw
 
@@ -168,23 +182,15 @@ class AnnealedImportanceSampler:
             raise _ops.FabhipError("u0 (uniform base draws) belongs to the fused spline-flow call; a RealNVP takes eps0 only")
         ops = _ops.load()
         flow, target = self._native_parts()
-        op = self.transition_operator
-        if bool(op.p_target) != bool(self.p_target) or (not self.p_target and op.alpha != self.alpha):
-            # the reference keeps the two in sync through FABModel.set_ais_target (core.py:102-110)
-            raise _ops.FabhipError("AIS and transition operator disagree on p_target / alpha")
+        kind, slots = operator_slots(self.transition_operator)
+        head = self._call_head(flow, target, kind)
         dev = flow._nf_model.q0.loc.device
         B, D, M = int(batch_size), flow.dim, self.n_intermediate_distributions
-        hmc = isinstance(op, HamiltonianMonteCarlo)
-        if not hmc and not isinstance(op, Metropolis):
-            raise _ops.FabhipError("transition_operator must be a fab_torch_amd HamiltonianMonteCarlo / Metropolis")
-        n_inner = op.n_outer if hmc else op.n_updates
+        hmc, n_inner = kind == _ops.TRANSITION_HMC, slots.n_inner
         f32 = dict(dtype=torch.float32, device=dev)
-        if eps0 is None:
-            eps0 = torch.randn((B, D), **f32)
-        eps0 = eps0.contiguous()
-        if noise_a is None and noise_b is None:
-            pass        # drawn inside the op, in this order, AFTER the chain initialisation is enqueued (the device works meanwhile)
-        else:
+        eps0 = torch.randn((B, D), **f32) if eps0 is None else eps0.contiguous()
+        # (both absent: drawn inside the op, in this order, AFTER the chain initialisation is enqueued - the device works meanwhile)
+        if noise_a is not None or noise_b is not None:
             if noise_a is None:
                 noise_a = torch.randn((M, n_inner, B, D), **f32)
             if noise_b is None:
@@ -192,8 +198,6 @@ class AnnealedImportanceSampler:
                            else torch.rand((M, n_inner, B), **f32))
             noise_a, noise_b = noise_a.contiguous(), noise_b.contiguous()
             assert noise_a.shape == (M, n_inner, B, D) and noise_b.shape == (M, n_inner, B)
-        betas = self._betas()
-        alpha = float(self.alpha) if self.alpha is not None else 0.0
         tau = self.resample_threshold
         if noise_r is not None:
             if tau is None:
@@ -202,18 +206,7 @@ class AnnealedImportanceSampler:
         # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
         call = ops.ais_run if tau is None else ops.ais_run_smc
         smc = () if tau is None else (tau, noise_r, bool(trace))
-        if hmc:
-            out = call(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
-                       _ops.TRANSITION_HMC, eps0, noise_a, noise_b, op.epsilons, op.common_epsilon,
-                       op.mass_vector, n_inner, op.L, float(op.max_grad), float(op.target_p_accept),
-                       not op.eval_mode, op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last,
-                       bool(want_base), _ops.precision_of(flow), *smc)
-        else:
-            out = call(*flow.native(), *target.native_target(), betas, alpha, bool(self.p_target),
-                       _ops.TRANSITION_METROPOLIS, eps0, noise_a, noise_b, op.noise_scalings, None, None,
-                       n_inner, 0, 0.0, float(op.target_prob_accept),
-                       bool(op.adjust_step_size and not op.eval_mode), None, None, None, None, bool(want_base),
-                       _ops.precision_of(flow), *smc)
+        out = call(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), *smc)
         if tau is not None:
             self.last_smc = tuple(out[10:14])
             out = out[:10]
@@ -241,27 +234,63 @@ class AnnealedImportanceSampler:
                 bool(self.p_target), _ops.precision_of(flow), op.L, op.n_outer, float(op.max_grad), float(op.target_p_accept),
                 bool(op.eval_mode), id(op.mass_vector), op.mass_vector._version, int(_ops.load().get_fast_mode()))
 
-    def _pf_new_state(self, flow, op, B, D):
-        M = self.n_intermediate_distributions
-        f32 = dict(dtype=torch.float32, device=flow._nf_model.q0.loc.device)
-        counts_stats = torch.zeros(18, **f32)                 # stats[16] | n_valid[2]: ONE device->host read at the end
-        # (the transition noise is DRAWN when the call itself runs - `normal_()` / `exponential_()` into these buffers, the draws
-        #  `torch.randn` / `empty().exponential_()` of the one-op call make - so that the generator is consumed in call order)
-        return {"eps0": torch.randn((B, D), **f32), "x": torch.empty((B, D), **f32), "lq": torch.empty(B, **f32),
-                "lp": torch.empty(B, **f32), "gq": torch.empty((B, D), **f32), "gp": torch.empty((B, D), **f32),
-                "log_w": torch.empty(B, **f32), "cs": counts_stats, "n_valid": counts_stats[16:18].view(torch.int32),
-                "stats": counts_stats[:16], "noise_a": torch.empty((M, op.n_outer, B, D), **f32),
-                "noise_b": torch.empty((M, op.n_outer, B), **f32)}
+    # ---- the fused call's arguments: ONE description, shared by every route into the ops ----------------------------------------
+    @property
+    def _alpha_arg(self) -> float:
+        """`alpha` as the ops take it (their `float alpha` is not read when the AIS target is p)."""
+        return float(self.alpha) if self.alpha is not None else 0.0
 
-    def _pf_phase(self, flow, target, op, st, phases, j0, j1):
+    def _call_head(self, flow, target, transition) -> tuple:
+        """The leading arguments of ais_run / ais_run_smc / ais_phase / ais_sharded_tuned: flow image, target, betas, alpha,
+        p_target, transition kind."""
+        op = self.transition_operator
+        if bool(op.p_target) != bool(self.p_target) or (not self.p_target and op.alpha != self.alpha):
+            # the reference keeps the two in sync through FABModel.set_ais_target (core.py:102-110)
+            raise _ops.FabhipError("AIS and transition operator disagree on p_target / alpha")
+        return (*flow.native(), *target.native_target(), self._betas(), self._alpha_arg, bool(self.p_target), transition)
+
+    def new_phase_state(self, b, eps0=None, noise_a=None, noise_b=None, draw_noise: bool = True, slab: bool = False) -> dict:
+        """The caller-owned tensors of one AIS call made in pieces (`enqueue_phase`): Point fields, log_w, the 18-word
+        stats[16] | n_valid[2] buffer that ONE device->host read fetches (_ops.read_counts_and_stats), the noise and, with
+        `slab`, the buffer of the acceptance sums of a deferred adaptation.  Noise that is not passed in is drawn here, in the
+        order the one-op call draws it (eps0, noise_a, noise_b); `draw_noise=False` only allocates noise_a / noise_b - the
+        prefetch path fills them (`normal_()` / `exponential_()`: the same draws) when the call they belong to runs, so that
+        the generator is consumed in call order."""
         ops = _ops.load()
-        alpha = float(self.alpha) if self.alpha is not None else 0.0
-        na, nb = st["noise_a"], st["noise_b"]                                   # (the INIT piece reads eps0 only)
-        ops.ais_phase(*flow.native(), *target.native_target(), self._betas(), alpha, bool(self.p_target), _ops.TRANSITION_HMC,
-                      int(phases), int(j0), int(j1), st["eps0"], na, nb, op.epsilons, op.common_epsilon, op.mass_vector,
-                      op.n_outer, op.L, float(op.max_grad), float(op.target_p_accept), not op.eval_mode, st["x"], st["lq"],
-                      st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], None, op._p_accept_first,
-                      op._p_accept_last, op._dist_first, op._dist_last, None, None, _ops.precision_of(flow))
+        flow, _ = self._native_parts()
+        kind, slots = operator_slots(self.transition_operator)
+        hmc, b, D, M, n = kind == _ops.TRANSITION_HMC, int(b), flow.dim, self.n_intermediate_distributions, int(slots.n_inner)
+        f32 = dict(dtype=torch.float32, device=flow._nf_model.q0.loc.device)
+        counts_stats = torch.zeros(18, **f32)
+        st = {"b": b, "cs": counts_stats, "stats": counts_stats[:16], "n_valid": counts_stats[16:18].view(torch.int32),
+              "eps0": torch.randn((b, D), **f32) if eps0 is None else eps0.contiguous()}
+        if not draw_noise:
+            st["noise_a"], st["noise_b"] = torch.empty((M, n, b, D), **f32), torch.empty((M, n, b), **f32)
+        else:
+            st["noise_a"] = torch.randn((M, n, b, D), **f32) if noise_a is None else noise_a.contiguous()
+            if noise_b is not None:
+                st["noise_b"] = noise_b.contiguous()
+            else:
+                st["noise_b"] = torch.empty((M, n, b), **f32).exponential_(1.0) if hmc else torch.rand((M, n, b), **f32)
+        st.update(x=torch.empty((b, D), **f32), lq=torch.empty(b, **f32), lp=torch.empty(b, **f32),
+                  gq=torch.empty((b, D), **f32) if hmc else None, gp=torch.empty((b, D), **f32) if hmc else None,
+                  log_w=torch.empty(b, **f32), slab=None)
+        if slab:
+            n_slab = ops.hmc_partials_floats(b) if hmc else ops.metropolis_partials_floats(b, M, n)
+            st["slab"] = torch.empty(int(n_slab), **f32)
+        return st
+
+    def enqueue_phase(self, st, phases, j0, j1, partials=None, tune: Optional[bool] = None, logging: bool = True):
+        """torch.ops.fabhip.ais_phase on a state of `new_phase_state`: the phases (FABHIP_AIS_INIT = 1, _FINISH = 2) and the
+        transitions j0 .. j1 of this sampler's call.  `tune` overrides the operator's own setting (with `partials` the
+        adaptation is deferred to the caller); `logging=False`: the operator's logging slots are left alone."""
+        flow, target = self._native_parts()
+        kind, s = operator_slots(self.transition_operator)
+        log = s[8:] if logging else (None, None, None, None)
+        _ops.load().ais_phase(*self._call_head(flow, target, kind), int(phases), int(j0), int(j1), st["eps0"], st["noise_a"],
+                              st["noise_b"], *s[:7], s.tune if tune is None else bool(tune), st["x"], st["lq"], st["lp"],
+                              st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], partials, *log, None, None,
+                              _ops.precision_of(flow))
 
     def _pf_take(self, key):
         """The prefetched piece made for `key`, if the generator is where the prefetch left it; else it is dropped (and, when only
@@ -277,24 +306,24 @@ class AnnealedImportanceSampler:
             torch.cuda.set_rng_state(before, dev)
         return None
 
-    def _sample_repeated(self, flow, target, op, B, key):
+    def _sample_repeated(self, B, key):
         """One call in two pieces with the next call's chain initialisation enqueued behind this call's read (see above)."""
-        D, M = flow.dim, self.n_intermediate_distributions
+        M = self.n_intermediate_distributions
         st = self._pf_take(key)
         if st is None:
-            st = self._pf_new_state(flow, op, B, D)
-            self._pf_phase(flow, target, op, st, 1, 1, 0)                        # FABHIP_AIS_INIT
+            st = self.new_phase_state(B, draw_noise=False)
+            self.enqueue_phase(st, 1, 1, 0)                                      # FABHIP_AIS_INIT (reads eps0 only)
         st["noise_a"].normal_()
         st["noise_b"].exponential_(1.0)
-        self._pf_phase(flow, target, op, st, 2, 1, M)                            # transitions 1 .. M, FABHIP_AIS_FINISH
+        self.enqueue_phase(st, 2, 1, M)                                          # transitions 1 .. M, FABHIP_AIS_FINISH
 
         dev = st["x"].device
 
         def enqueue_next():
             before = torch.cuda.get_rng_state(dev)
-            nxt = self._pf_new_state(flow, op, B, D)
+            nxt = self.new_phase_state(B, draw_noise=False)
             after = torch.cuda.get_rng_state(dev)
-            self._pf_phase(flow, target, op, nxt, 1, 1, 0)
+            self.enqueue_phase(nxt, 1, 1, 0)
             self.__dict__["_pf_state"] = (key, nxt, before, after, dev)
         host, counts = _ops.read_counts_and_stats(st["n_valid"], st["stats"], between=enqueue_next)
         return Point(st["x"], st["lq"], st["lp"], st["gq"], st["gp"]), st["log_w"], host, counts
@@ -345,7 +374,7 @@ class AnnealedImportanceSampler:
         ops = _ops.load()
         op = self.transition_operator
         B, M = int(batch_size), self.n_intermediate_distributions
-        alpha = float(self.alpha) if self.alpha is not None else 0.0
+        alpha = self._alpha_arg
         x, log_q0 = self.base_distribution.sample_and_log_prob((B,))
         point = create_point_generic(x, self.base_distribution.log_prob, self.target_log_prob,
                                      with_grad=op.uses_grad_info, log_q_x=log_q0)
@@ -433,15 +462,13 @@ class AnnealedImportanceSampler:
         if (not fused_spline and not smc_on and self.prefetch and eps0 is None and noise_a is None and noise_b is None
                 and isinstance(self.transition_operator, HamiltonianMonteCarlo)):
             flow, target = self._native_parts()
-            op = self.transition_operator
-            if bool(op.p_target) == bool(self.p_target) and (self.p_target or op.alpha == self.alpha):
-                flow.native()                                                    # (the image - and its key - of the current parameters)
-                key = self._pf_key(flow, target, op, int(batch_size))
-                if self.__dict__.get("_pf_last_key") == key:
-                    repeated = self._sample_repeated(flow, target, op, int(batch_size), key)
-                else:
-                    self._pf_take(None)                                          # (drops a piece made for another key)
-                self.__dict__["_pf_last_key"] = key
+            flow.native()                                                        # (the image - and its key - of the current parameters)
+            key = self._pf_key(flow, target, self.transition_operator, int(batch_size))
+            if self.__dict__.get("_pf_last_key") == key:
+                repeated = self._sample_repeated(int(batch_size), key)
+            else:
+                self._pf_take(None)                                              # (drops a piece made for another key)
+            self.__dict__["_pf_last_key"] = key
         if repeated is not None:
             point, log_w, host, (n_init, n_end) = repeated
         else:

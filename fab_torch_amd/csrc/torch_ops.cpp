@@ -752,6 +752,32 @@ void spline_hmc_transition(const Tensor& packed, int64_t dim, int64_t n_layers, 
     chk(fabhip_spline_hmc_transition(&a, stream_of(x)), "spline_hmc_transition");
 }
 
+// What the whole-call AIS ops (ais_run, ais_run_smc, spline_ais_run) and their argument structs have in common.
+// The four logging slots (hmc.py:173-183, store_info): at least n_inner / 1 floats each.
+template <class Args>
+void fill_logging_slots(Args& a, int64_t n_inner, const Tensor& ref, const optional<Tensor>& p_accept_first,
+                        const optional<Tensor>& p_accept_last, const optional<Tensor>& avg_distance_first,
+                        const optional<Tensor>& avg_distance_last) {
+    a.p_accept_first = fpmn_opt(p_accept_first, n_inner, ref, "p_accept_first", true);
+    a.p_accept_last = fpmn_opt(p_accept_last, n_inner, ref, "p_accept_last", true);
+    a.avg_distance_first = fpmn_opt(avg_distance_first, 1, ref, "avg_distance_first", true);
+    a.avg_distance_last = fpmn_opt(avg_distance_last, 1, ref, "avg_distance_last", true);
+}
+// The outputs besides the Point and log_w: stats[16] | n_valid[2] as views of ONE 18-word buffer (one device->host copy,
+// _ops.read_counts_and_stats; every word is written by the call: the counts and statistics by the phase tails, stats[6..15] = 0)
+// and, with want_base, the chains' starting points and their log p - log q.
+struct AisOutputs { Tensor stats, n_valid, base_x, base_lw; };
+template <class Args>
+AisOutputs alloc_ais_outputs(Args& a, int64_t B, int64_t dim, const Tensor& like, bool want_base) {
+    Tensor counts_stats = at::empty({18}, like.options());
+    AisOutputs o{counts_stats.narrow(0, 0, 16), counts_stats.narrow(0, 16, 2).view(at::kInt),
+                 want_base ? fempty({B, dim}, like) : fempty({0}, like), want_base ? fempty({B}, like) : fempty({0}, like)};
+    a.n_valid = o.n_valid.data_ptr<int32_t>(); a.stats = o.stats.data_ptr<float>();
+    a.base_x = want_base ? o.base_x.data_ptr<float>() : nullptr;
+    a.base_log_w = want_base ? o.base_lw.data_ptr<float>() : nullptr;
+    return o;
+}
+
 // The spline family's ais_run (fabhip_spline_ais_run): same outputs as ais_run.
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> spline_ais_run(
     const Tensor& packed, int64_t dim, int64_t n_layers, int64_t hidden, int64_t kind, at::ArrayRef<double> prm,
@@ -779,25 +805,16 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
     Tensor x = fempty({B, dim}, eps0), lq = fempty({B}, eps0), lp = fempty({B}, eps0), log_w = fempty({B}, eps0);
     Tensor gq = fempty({B, dim}, eps0), gp = fempty({B, dim}, eps0);
-    Tensor counts_stats = at::empty({18}, eps0.options());      // one device->host copy (_ops.read_counts_and_stats); every word is
-                                                                // written by the call (the counts and statistics by the phase tails, stats[6..15] = 0)
-    Tensor stats = counts_stats.narrow(0, 0, 16), n_valid = counts_stats.narrow(0, 16, 2).view(at::kInt);
-    Tensor base_x = want_base ? fempty({B, dim}, eps0) : fempty({0}, eps0);
-    Tensor base_lw = want_base ? fempty({B}, eps0) : fempty({0}, eps0);
     a.point = fabhip_point{x.data_ptr<float>(), lq.data_ptr<float>(), lp.data_ptr<float>(), gq.data_ptr<float>(),
                            gp.data_ptr<float>()};
-    a.log_w = log_w.data_ptr<float>(); a.n_valid = n_valid.data_ptr<int32_t>(); a.stats = stats.data_ptr<float>();
-    a.p_accept_first = fpmn_opt(p_accept_first, n_outer, eps0, "p_accept_first", true);
-    a.p_accept_last = fpmn_opt(p_accept_last, n_outer, eps0, "p_accept_last", true);
-    a.avg_distance_first = fpmn_opt(avg_distance_first, 1, eps0, "avg_distance_first", true);
-    a.avg_distance_last = fpmn_opt(avg_distance_last, 1, eps0, "avg_distance_last", true);
-    a.base_x = want_base ? base_x.data_ptr<float>() : nullptr;
-    a.base_log_w = want_base ? base_lw.data_ptr<float>() : nullptr;
+    a.log_w = log_w.data_ptr<float>();
+    const AisOutputs o = alloc_ais_outputs(a, B, dim, eps0, want_base);
+    fill_logging_slots(a, n_outer, eps0, p_accept_first, p_accept_last, avg_distance_first, avg_distance_last);
     const size_t nb = fabhip_spline_ais_workspace_bytes(a.flow.dim, a.flow.n_layers, a.flow.hidden, B);
     Tensor ws = scratch(nb, eps0);
     a.workspace = aligned(ws); a.workspace_bytes = nb;
     chk(fabhip_spline_ais_run(&a, stream_of(eps0)), "spline_ais_run");
-    return {x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw};
+    return {x, lq, lp, gq, gp, log_w, o.n_valid, o.stats, o.base_x, o.base_lw};
 }
 
 Tensor anneal_log_prob(const Tensor& log_q, const Tensor& log_p, double beta, double alpha, bool p_target) {
@@ -853,6 +870,56 @@ void metropolis_generic_accept(const Tensor& x_new, const Tensor& new_lq, const 
 //   (x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid int32[2], stats float[16], base_x, base_log_w)
 // grad_* are empty for Metropolis, base_* are empty unless want_base.
 // ------------------------------------------------------------------------------------------------------------------
+// fabhip_ais_args and what it points to for the length of the C call.  `fill_ais_args` writes the part every AIS op shares;
+// the op adds the noise and the state tensors (the ones it allocates, or the caller's).
+struct AisCall {
+    fabhip_ais_args a;
+    std::vector<double> betas;      // a.betas
+    Tensor ws;                      // a.workspace
+    int64_t B = 0, M = 0;
+    bool hmc = false;
+    AisCall() = default;
+    AisCall(const AisCall&) = delete;               // (a.betas points into this object's vector)
+    AisCall& operator=(const AisCall&) = delete;
+};
+
+// flow, target, B / M / betas, alpha / p_target / transition, the operator's step state and settings, the logging slots and the
+// workspace (`smc_on`: with the resampling step's share).  `ref`: the tensor whose device and stream the call is enqueued on.
+void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
+                   at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales,
+                   at::ArrayRef<double> betas, double alpha, bool p_target, int64_t transition, int64_t B, const Tensor& ref,
+                   const Tensor& step_state, const optional<Tensor>& common_epsilon, const optional<Tensor>& mass,
+                   int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune,
+                   const optional<Tensor>& p_accept_first, const optional<Tensor>& p_accept_last,
+                   const optional<Tensor>& avg_distance_first, const optional<Tensor>& avg_distance_last, int64_t precision,
+                   bool smc_on) {
+    fabhip_ais_args& a = c.a;
+    a.flow = make_flow(packed, dim, n_layers, width, precision);
+    a.target = make_target(kind, prm, locs, scales, dim);
+    const int64_t M = (int64_t)betas.size() - 2;
+    const bool hmc = transition == FABHIP_TRANSITION_HMC;
+    TORCH_CHECK(M >= 1, "fabhip: betas must hold M + 2 values");
+    TORCH_CHECK(n_inner >= 1, "fabhip: n_inner (HMC outer loops / Metropolis updates per transition) must be >= 1");
+    TORCH_CHECK(hmc || transition == FABHIP_TRANSITION_METROPOLIS, "fabhip: unknown transition kind ", transition);
+    TORCH_CHECK(!hmc || (common_epsilon.has_value() && mass.has_value()),
+                "fabhip: an HMC AIS run needs common_epsilon and the mass vector");
+    c.B = B; c.M = M; c.hmc = hmc;
+    c.betas.assign(betas.begin(), betas.end());
+    a.B = B; a.M = (int32_t)M; a.betas = c.betas.data();
+    a.alpha = alpha; a.p_target = p_target ? 1 : 0; a.transition = (int32_t)transition;
+    a.eps0 = a.noise_a = a.noise_b = nullptr;
+    a.step_state = fpmn(step_state, M * n_inner, ref, "step_state");
+    a.common_epsilon = fpmn_opt(common_epsilon, 1, ref, "common_epsilon", true);
+    a.mass = mass.has_value() ? fpn(*mass, dim, ref, "mass") : nullptr;
+    a.n_inner = (int32_t)n_inner; a.L = (int32_t)L; a.max_grad = (float)max_grad;
+    a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
+    fill_logging_slots(a, n_inner, ref, p_accept_first, p_accept_last, avg_distance_first, avg_distance_last);
+    const size_t nb = smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
+                             : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
+    c.ws = scratch(nb, ref);
+    a.workspace = aligned(c.ws); a.workspace_bytes = nb;
+}
+
 // SMC mode of the AIS ops (fabhip_smc_args): `tau` absent = the plain call through the same entry points.  noise_r [M] float64
 // (absent: drawn from the default generator AFTER the transition noise); the per-transition records are allocated here.
 struct SmcOp {
@@ -870,50 +937,42 @@ static Tensor smc_uniforms(const optional<Tensor>& noise_r, int64_t M, const Ten
     return *noise_r;
 }
 
+// The plain op of an implementation whose first parameter is its SMC mode: the same parameter list without it, NULL passed.
+template <auto Impl> struct Plain;
+template <class R, class S, class... A, R (*Impl)(S*, A...)> struct Plain<Impl> {
+    static R op(A... a) { return Impl(nullptr, std::forward<A>(a)...); }
+};
+
+// `smc` == nullptr: the plain op (ais_run) - the same entry points of the C ABI with a NULL fabhip_smc_args.
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run_impl(
-    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    SmcOp* smc, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
     const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
     bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
     const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
     int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
     optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision, SmcOp* smc) {
+    int64_t precision) {
     c10::DeviceGuard g(eps0.device());
     const bool smc_on = smc != nullptr && smc->tau.has_value();
     // noise_a / noise_b absent: drawn HERE, from the default generator in the order the Python side draws them (normal
     // [M, n_inner, B, dim], then exponential(1) / uniform [M, n_inner, B]) - but AFTER the chain initialisation is enqueued, so the
     // device works while the host launches the draws (FABHIP_AIS_CONTINUE)
-    const bool draw_inside = !noise_a_in.has_value() || !noise_b_in.has_value();
     TORCH_CHECK(noise_a_in.has_value() == noise_b_in.has_value(), "fabhip: pass both noise tensors or neither");
-    Tensor noise_a = draw_inside ? Tensor() : *noise_a_in, noise_b = draw_inside ? Tensor() : *noise_b_in;
-    fabhip_ais_args a;
-    a.flow = make_flow(packed, dim, n_layers, width, precision);
-    a.target = make_target(kind, prm, locs, scales, dim);
+    const bool draw_inside = !noise_a_in.has_value();
     TORCH_CHECK(eps0.dim() == 2 && eps0.size(1) == dim, "fabhip: eps0 must be [B, dim]");
-    const int64_t B = eps0.size(0), M = (int64_t)betas.size() - 2;
-    TORCH_CHECK(M >= 1, "fabhip: betas must hold M + 2 values");
-    TORCH_CHECK(draw_inside || (noise_a.numel() == M * n_inner * B * dim && noise_b.numel() == M * n_inner * B),
-                "fabhip: AIS noise shapes");
-    TORCH_CHECK(step_state.numel() == M * n_inner, "fabhip: step-size state must be [M, n_inner]");
-    const bool hmc = transition == FABHIP_TRANSITION_HMC;
-    a.B = B; a.M = (int32_t)M;
-    std::vector<double> bt(betas.begin(), betas.end());
-    a.betas = bt.data();
-    a.alpha = alpha; a.p_target = p_target ? 1 : 0; a.transition = (int32_t)transition;
-    TORCH_CHECK(n_inner >= 1, "fabhip: n_inner (HMC outer loops / Metropolis updates per transition) must be >= 1");
-    TORCH_CHECK(hmc || transition == FABHIP_TRANSITION_METROPOLIS, "fabhip: unknown transition kind ", transition);
-    TORCH_CHECK(!hmc || (common_epsilon.has_value() && mass.has_value()),
-                "fabhip: an HMC AIS run needs common_epsilon and the mass vector");
+    AisCall c;
+    fill_ais_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0.size(0), eps0,
+                  step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first, p_accept_last,
+                  avg_distance_first, avg_distance_last, precision, smc_on);
+    fabhip_ais_args& a = c.a;
+    const int64_t B = c.B, M = c.M;
+    const bool hmc = c.hmc;
     a.eps0 = fp(eps0, "eps0");
-    a.noise_a = a.noise_b = nullptr;
+    Tensor noise_a, noise_b;
     if (!draw_inside) {
+        noise_a = *noise_a_in; noise_b = *noise_b_in;
         a.noise_a = fpn(noise_a, M * n_inner * B * dim, eps0, "noise_a"); a.noise_b = fpn(noise_b, M * n_inner * B, eps0, "noise_b");
     }
-    a.step_state = fpmn(step_state, M * n_inner, eps0, "step_state");
-    a.common_epsilon = fpmn_opt(common_epsilon, 1, eps0, "common_epsilon", true);
-    a.mass = mass.has_value() ? fpn(*mass, dim, eps0, "mass") : nullptr;
-    a.n_inner = (int32_t)n_inner; a.L = (int32_t)L; a.max_grad = (float)max_grad;
-    a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
     // the outputs are views of ONE allocation (each padded to 256 bytes): one trip through the caching allocator instead of six
     // on the host path the GPU waits for
     auto pad64 = [](int64_t n) { return (n + 63) / 64 * 64; };
@@ -926,40 +985,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     };
     Tensor x = take(B, dim), lq = take(B, 0), lp = take(B, 0), log_w = take(B, 0);
     Tensor gq = hmc ? take(B, dim) : fempty({0}, eps0), gp = hmc ? take(B, dim) : fempty({0}, eps0);
-    Tensor counts_stats = at::empty({18}, eps0.options());      // one device->host copy (_ops.read_counts_and_stats); every word is
-                                                                // written by the call (the counts and statistics by the phase tails, stats[6..15] = 0)
-    Tensor stats = counts_stats.narrow(0, 0, 16), n_valid = counts_stats.narrow(0, 16, 2).view(at::kInt);
-    Tensor base_x = want_base ? fempty({B, dim}, eps0) : fempty({0}, eps0);
-    Tensor base_lw = want_base ? fempty({B}, eps0) : fempty({0}, eps0);
     a.point = fabhip_point{x.data_ptr<float>(), lq.data_ptr<float>(), lp.data_ptr<float>(),
                            hmc ? gq.data_ptr<float>() : nullptr, hmc ? gp.data_ptr<float>() : nullptr};
-    a.log_w = log_w.data_ptr<float>(); a.n_valid = n_valid.data_ptr<int32_t>(); a.stats = stats.data_ptr<float>();
-    a.p_accept_first = fpmn_opt(p_accept_first, n_inner, eps0, "p_accept_first", true);
-    a.p_accept_last = fpmn_opt(p_accept_last, n_inner, eps0, "p_accept_last", true);
-    a.avg_distance_first = fpmn_opt(avg_distance_first, 1, eps0, "avg_distance_first", true);
-    a.avg_distance_last = fpmn_opt(avg_distance_last, 1, eps0, "avg_distance_last", true);
-    a.base_x = want_base ? base_x.data_ptr<float>() : nullptr;
-    a.base_log_w = want_base ? base_lw.data_ptr<float>() : nullptr;
-    const size_t nb = smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
-                             : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
-    Tensor ws = scratch(nb, eps0);
-    a.workspace = aligned(ws); a.workspace_bytes = nb;
-    if (smc == nullptr) {                                      // the plain ops: the entry points they have always called
-        if (!draw_inside) {
-            chk(fabhip_ais_run(&a, stream_of(eps0)), "ais_run");
-        } else {
-            chk(fabhip_ais_phase(&a, FABHIP_AIS_INIT, 1, 0, nullptr, stream_of(eps0)), "ais_run (chain initialisation)");
-            noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
-            noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
-            a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
-            chk(fabhip_ais_phase(&a, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, stream_of(eps0)),
-                "ais_run (transitions)");
-        }
-        return {x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw};
-    }
-    fabhip_smc_args sa;
-    sa.enabled = smc_on ? 1 : 0; sa.only_resample = 0; sa.tau = smc_on ? *smc->tau : 0.0;
-    sa.u = nullptr; sa.resampled = nullptr; sa.ess = nullptr; sa.ancestors = nullptr; sa.log_w_pre = nullptr;
+    a.log_w = log_w.data_ptr<float>();
+    const AisOutputs o = alloc_ais_outputs(a, B, dim, eps0, want_base);
+    fabhip_smc_args sa = {};                                   // (records: NULL until smc_outputs)
+    sa.enabled = smc_on ? 1 : 0; sa.tau = smc_on ? *smc->tau : 0.0;
     auto smc_outputs = [&]() {                                 // (after the transition noise: the generator's order of draws)
         if (!smc_on) return;
         smc->u = smc_uniforms(smc->noise_r, M, eps0);
@@ -972,32 +1003,21 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
             sa.ancestors = smc->ancestors.data_ptr<int32_t>(); sa.log_w_pre = smc->log_w_pre.data_ptr<float>();
         }
     };
+    const fabhip_smc_args* sap = smc != nullptr ? &sa : nullptr;
+    const fabhip_stream_t st = stream_of(eps0);
     if (!draw_inside) {
         smc_outputs();
-        chk(fabhip_ais_run_smc(&a, &sa, stream_of(eps0)), "ais_run_smc");
+        chk(fabhip_ais_run_smc(&a, sap, st), "ais_run");
     } else {
-        chk(fabhip_ais_phase_smc(&a, &sa, FABHIP_AIS_INIT, 1, 0, nullptr, stream_of(eps0)), "ais_run_smc (chain initialisation)");
+        chk(fabhip_ais_phase_smc(&a, sap, FABHIP_AIS_INIT, 1, 0, nullptr, st), "ais_run (chain initialisation)");
         noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
         noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
         a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
         smc_outputs();
-        chk(fabhip_ais_phase_smc(&a, &sa, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, stream_of(eps0)),
-            "ais_run_smc (transitions)");
+        chk(fabhip_ais_phase_smc(&a, sap, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
+            "ais_run (transitions)");
     }
-    return {x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run(
-    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
-    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
-    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
-    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
-    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision) {
-    return ais_run_impl(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0, noise_a_in,
-                        noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first,
-                        p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, nullptr);
+    return {x, lq, lp, gq, gp, log_w, o.n_valid, o.stats, o.base_x, o.base_lw};
 }
 
 // ais_run with the SMC mode: the ten outputs of ais_run, then resampled int32[M], ess float[M], ancestors int32[M, B],
@@ -1012,9 +1032,9 @@ std::vector<Tensor> ais_run_smc(
     int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace) {
     SmcOp smc;
     smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace;
-    auto t = ais_run_impl(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
                           noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, &smc);
+                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
     auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
     return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
             std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
@@ -1022,127 +1042,61 @@ std::vector<Tensor> ais_run_smc(
 }
 
 // The same call in pieces (fabhip_ais_phase): the state tensors are the caller's, in/out across the phases of one AIS
-// run.  Used when chains are sharded over ranks and the step sizes adapt on the acceptance of ALL chains: one transition
-// per call with `partials`, the caller all-gathers the slabs and calls hmc_adapt_gathered (fab_torch_amd/parallel.py).
-// `group_name` == nullptr: the phases / transitions the caller names, once.  Otherwise the WHOLE tuned call of one shard:
-// INIT, then per transition {transition with the adaptation deferred, slab all-gather over the named c10d process group,
-// step-size rule on the gathered slabs}, FINISH - see ais_sharded_tuned below.  Returns the number of collectives issued.
-int64_t ais_phase_core(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
-               const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-               bool p_target, int64_t transition, int64_t phases, int64_t j_begin, int64_t j_end,
-               const optional<Tensor>& eps0, const Tensor& noise_a, const Tensor& noise_b, Tensor step_state,
-               optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
-               double target_p_accept, bool tune, Tensor x, Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q,
-               optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
-               optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
-               optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision,
-               const std::string* group_name, const fabhip_smc_args* smc = nullptr) {
-    c10::DeviceGuard g(x.device());
-    fabhip_ais_args a;
-    a.flow = make_flow(packed, dim, n_layers, width, precision);
-    a.target = make_target(kind, prm, locs, scales, dim);
+// run.  `ais_phase_args` fills the call's arguments and returns the checked slab pointer (`partials`: the acceptance sums of a
+// deferred adaptation); the ops below decide what to run on them.
+float* ais_phase_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
+                      at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales,
+                      at::ArrayRef<double> betas, double alpha, bool p_target, int64_t transition, const optional<Tensor>& eps0,
+                      const Tensor& noise_a, const Tensor& noise_b, const Tensor& step_state,
+                      const optional<Tensor>& common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L,
+                      double max_grad, double target_p_accept, bool tune, const Tensor& x, const Tensor& log_q,
+                      const Tensor& log_p, const optional<Tensor>& grad_log_q, const optional<Tensor>& grad_log_p,
+                      const Tensor& log_w, const Tensor& n_valid, const Tensor& stats, const optional<Tensor>& partials,
+                      const optional<Tensor>& p_accept_first, const optional<Tensor>& p_accept_last,
+                      const optional<Tensor>& avg_distance_first, const optional<Tensor>& avg_distance_last,
+                      const optional<Tensor>& base_x, const optional<Tensor>& base_log_w, int64_t precision, bool smc_on) {
     TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
-    const int64_t B = x.size(0), M = (int64_t)betas.size() - 2;
-    TORCH_CHECK(M >= 1, "fabhip: betas must hold M + 2 values");
-    TORCH_CHECK(n_inner >= 1, "fabhip: n_inner must be >= 1");
-    const bool hmc = transition == FABHIP_TRANSITION_HMC;
-    TORCH_CHECK(hmc || transition == FABHIP_TRANSITION_METROPOLIS, "fabhip: unknown transition kind ", transition);
-    TORCH_CHECK(!hmc || (common_epsilon.has_value() && mass.has_value() && grad_log_q.has_value() && grad_log_p.has_value()),
-                "fabhip: an HMC AIS run needs common_epsilon, the mass vector and the gradient fields of the Point");
-    a.B = B; a.M = (int32_t)M;
-    std::vector<double> bt(betas.begin(), betas.end());
-    a.betas = bt.data();
-    a.alpha = alpha; a.p_target = p_target ? 1 : 0; a.transition = (int32_t)transition;
+    fill_ais_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, x.size(0), x,
+                  step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first, p_accept_last,
+                  avg_distance_first, avg_distance_last, precision, smc_on);
+    fabhip_ais_args& a = c.a;
+    const int64_t B = c.B, M = c.M;
+    TORCH_CHECK(!c.hmc || (grad_log_q.has_value() && grad_log_p.has_value()),
+                "fabhip: an HMC AIS run needs the gradient fields of the Point");
     a.eps0 = eps0.has_value() ? fpn(*eps0, B * dim, x, "eps0") : nullptr;
     a.noise_a = fpn(noise_a, M * n_inner * B * dim, x, "noise_a"); a.noise_b = fpn(noise_b, M * n_inner * B, x, "noise_b");
-    a.step_state = fpmn(step_state, M * n_inner, x, "step_state");
-    a.common_epsilon = fpmn_opt(common_epsilon, 1, x, "common_epsilon", true);
-    a.mass = mass.has_value() ? fpn(*mass, dim, x, "mass") : nullptr;
-    a.n_inner = (int32_t)n_inner; a.L = (int32_t)L; a.max_grad = (float)max_grad;
-    a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
     a.point = fabhip_point{fpm(x, "x"), fpmn(log_q, B, x, "log_q"), fpmn(log_p, B, x, "log_p"),
-                           hmc ? fpmn(*grad_log_q, B * dim, x, "grad_log_q") : nullptr,
-                           hmc ? fpmn(*grad_log_p, B * dim, x, "grad_log_p") : nullptr};
+                           c.hmc ? fpmn(*grad_log_q, B * dim, x, "grad_log_q") : nullptr,
+                           c.hmc ? fpmn(*grad_log_p, B * dim, x, "grad_log_p") : nullptr};
     a.log_w = fpmn(log_w, B, x, "log_w");
     need(n_valid, at::kInt, "n_valid"); need_n(n_valid, 2, x, "n_valid");
     a.n_valid = n_valid.data_ptr<int32_t>();
     a.stats = fpmn(stats, 16, x, "stats");
-    a.p_accept_first = fpmn_opt(p_accept_first, n_inner, x, "p_accept_first", true);
-    a.p_accept_last = fpmn_opt(p_accept_last, n_inner, x, "p_accept_last", true);
-    a.avg_distance_first = fpmn_opt(avg_distance_first, 1, x, "avg_distance_first", true);
-    a.avg_distance_last = fpmn_opt(avg_distance_last, 1, x, "avg_distance_last", true);
     a.base_x = fpmn_opt(base_x, B * dim, x, "base_x");
     a.base_log_w = fpmn_opt(base_log_w, B, x, "base_log_w");
-    const size_t nb = (smc && smc->enabled) ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
-                                            : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
-    Tensor ws = scratch(nb, x);
-    a.workspace = aligned(ws); a.workspace_bytes = nb;
-    float* slab = fpmn_opt(partials, hmc ? fabhip_hmc_partials_floats(B)
-                                         : fabhip_metropolis_partials_floats(B, (int32_t)M, (int32_t)n_inner), x, "partials");
-    if (group_name == nullptr) {
-        if (smc) chk(fabhip_ais_phase_smc(&a, smc, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)),
-                     "ais_phase_smc");
-        else chk(fabhip_ais_phase(&a, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)), "ais_phase");
-        return 0;
-    }
-    // ---- one shard's tuned call: the loop fab_torch_amd/parallel.py stepped from Python in rounds 2 - 4 ----
-    TORCH_CHECK(hmc && n_inner == 1 && slab != nullptr,
-                "fabhip: ais_sharded_tuned is HMC with n_outer == 1 and needs the acceptance slab (hmc_partials_floats(B) floats)");
-    auto pg = c10d::resolve_process_group(*group_name);
-    const int64_t world = pg->getSize(), nslab = fabhip_hmc_partials_floats(B);
-    // RCCL ("nccl") takes the device slab as it is: the collective is ordered behind the transition on the current stream
-    // and Work::wait() orders the stream behind the collective - the host never blocks.  A host-only backend (gloo: the
-    // CPU-side tests of the N > 1 path, two ranks on a one-GPU box) is fed through the host.
-    bool device_collective = false;
-    try {
-        device_collective = pg->getBackend(c10::DeviceType::CUDA)->getBackendName() == "nccl";
-    } catch (const std::exception&) {                     // no backend registered for device tensors: through the host
-    }
-    Tensor gathered = fempty({world * nslab}, x), host_in, host_out;
-    if (!device_collective) {
-        host_in = at::empty({nslab}, at::TensorOptions().dtype(at::kFloat).device(at::kCPU));
-        host_out = at::empty({world * nslab}, host_in.options());
-    }
-    const fabhip_stream_t st = stream_of(x);
-    chk(fabhip_ais_phase(&a, FABHIP_AIS_INIT, 1, 0, nullptr, st), "ais_sharded_tuned (chain initialisation)");
-    int64_t n_collectives = 0;
-    for (int64_t j = 1; j <= M; ++j) {
-        chk(fabhip_ais_phase(&a, 0, (int32_t)j, (int32_t)j, slab, st), "ais_sharded_tuned (transition)");
-        if (world > 1 || device_collective) {          // (a one-rank RCCL group still runs the collective: the path a node takes)
-            if (device_collective) {
-                pg->_allgather_base(gathered, *partials)->wait();
-            } else {
-                host_in.copy_(*partials);
-                pg->_allgather_base(host_out, host_in)->wait();
-                gathered.copy_(host_out);
-            }
-            ++n_collectives;
-        } else {
-            gathered.copy_(*partials);
-        }
-        float* pa = j == 1 ? a.p_accept_first : (j == M ? a.p_accept_last : nullptr);        // hmc.py:173-183 (store_info)
-        float* ad = j == 1 ? a.avg_distance_first : (j == M ? a.avg_distance_last : nullptr);
-        chk(fabhip_hmc_adapt_gathered(gathered.data_ptr<float>(), (int32_t)world, B, a.step_state + (j - 1), a.common_epsilon,
-                                      a.target_p_accept, 1, pa, ad, st),
-            "ais_sharded_tuned (step-size rule on the gathered slabs)");
-    }
-    chk(fabhip_ais_phase(&a, FABHIP_AIS_FINISH, 1, 0, nullptr, st), "ais_sharded_tuned (chain end)");
-    return n_collectives;
+    return fpmn_opt(partials, c.hmc ? fabhip_hmc_partials_floats(B)
+                                    : fabhip_metropolis_partials_floats(B, (int32_t)M, (int32_t)n_inner), x, "partials");
 }
 
-void ais_phase(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
-               const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-               bool p_target, int64_t transition, int64_t phases, int64_t j_begin, int64_t j_end,
-               const optional<Tensor>& eps0, const Tensor& noise_a, const Tensor& noise_b, Tensor step_state,
-               optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
-               double target_p_accept, bool tune, Tensor x, Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q,
-               optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
-               optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
-               optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision) {
-    ais_phase_core(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, phases, j_begin,
-                   j_end, eps0, noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                   x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
-                   avg_distance_first, avg_distance_last, base_x, base_log_w, precision, nullptr);
+// ais_phase / ais_phase_smc: the phases and transitions the caller names, once.  `smc` == nullptr: the plain op.
+void ais_phase_core(const fabhip_smc_args* smc, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
+                    at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales,
+                    at::ArrayRef<double> betas, double alpha, bool p_target, int64_t transition, int64_t phases, int64_t j_begin,
+                    int64_t j_end, const optional<Tensor>& eps0, const Tensor& noise_a, const Tensor& noise_b, Tensor step_state,
+                    optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
+                    double target_p_accept, bool tune, Tensor x, Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q,
+                    optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
+                    optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
+                    optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision) {
+    c10::DeviceGuard g(x.device());
+    AisCall c;
+    float* slab = ais_phase_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                                 noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                                 x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first,
+                                 p_accept_last, avg_distance_first, avg_distance_last, base_x, base_log_w, precision,
+                                 smc != nullptr && smc->enabled);
+    chk(fabhip_ais_phase_smc(&c.a, smc, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)),
+        smc != nullptr ? "ais_phase_smc" : "ais_phase");
 }
 
 // ais_phase with the SMC mode: transition j's phase starts with its resampling step (`only_resample`: and ends there).  The
@@ -1159,9 +1113,8 @@ void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t 
                    optional<double> tau, const optional<Tensor>& noise_r, bool only_resample, optional<Tensor> resampled,
                    optional<Tensor> ess, optional<Tensor> ancestors, optional<Tensor> log_w_pre) {
     const int64_t B = x.size(0), M = (int64_t)betas.size() - 2;
-    fabhip_smc_args sa;
+    fabhip_smc_args sa = {};
     sa.enabled = tau.has_value() ? 1 : 0; sa.only_resample = only_resample ? 1 : 0; sa.tau = tau.has_value() ? *tau : 0.0;
-    sa.u = nullptr; sa.resampled = nullptr; sa.ess = nullptr; sa.ancestors = nullptr; sa.log_w_pre = nullptr;
     if (sa.enabled) {
         TORCH_CHECK(noise_r.has_value(), "fabhip: ais_phase_smc needs noise_r (float64 [M]) when tau is given");
         sa.u = smc_uniforms(noise_r, M, x).data_ptr<double>();
@@ -1175,10 +1128,10 @@ void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t 
         sa.ess = fpmn_opt(ess, M, x, "ess");
         sa.log_w_pre = fpmn_opt(log_w_pre, M * B, x, "log_w_pre");
     }
-    ais_phase_core(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, phases, j_begin,
+    ais_phase_core(&sa, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, phases, j_begin,
                    j_end, eps0, noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
                    x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
-                   avg_distance_first, avg_distance_last, base_x, base_log_w, precision, nullptr, &sa);
+                   avg_distance_first, avg_distance_last, base_x, base_log_w, precision);
 }
 
 // The decision of the SMC step alone (fabhip_smc_decide) for samplers that step their transitions from Python:
@@ -1265,10 +1218,55 @@ int64_t ais_sharded_tuned(const Tensor& packed, int64_t dim, int64_t n_layers, i
                           optional<Tensor> p_accept_first, optional<Tensor> p_accept_last,
                           optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, int64_t precision,
                           std::string group_name) {
-    return ais_phase_core(packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, 0, 1, 0, eps0,
-                          noise_a, noise_b, step_state, common_epsilon, mass, 1, L, max_grad, target_p_accept, true, x, log_q,
-                          log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
-                          avg_distance_first, avg_distance_last, c10::nullopt, c10::nullopt, precision, &group_name);
+    c10::DeviceGuard g(x.device());
+    AisCall c;
+    float* slab = ais_phase_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                                 noise_a, noise_b, step_state, common_epsilon, mass, 1, L, max_grad, target_p_accept, true, x,
+                                 log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first,
+                                 p_accept_last, avg_distance_first, avg_distance_last, c10::nullopt, c10::nullopt, precision, false);
+    const fabhip_ais_args& a = c.a;
+    const int64_t B = c.B, M = c.M;
+    TORCH_CHECK(c.hmc, "fabhip: ais_sharded_tuned is HMC with n_outer == 1 (the acceptance slab: hmc_partials_floats(B) floats)");
+    auto pg = c10d::resolve_process_group(group_name);
+    const int64_t world = pg->getSize(), nslab = fabhip_hmc_partials_floats(B);
+    // RCCL ("nccl") takes the device slab as it is: the collective is ordered behind the transition on the current stream
+    // and Work::wait() orders the stream behind the collective - the host never blocks.  A host-only backend (gloo: the
+    // CPU-side tests of the N > 1 path, two ranks on a one-GPU box) is fed through the host.
+    bool device_collective = false;
+    try {
+        device_collective = pg->getBackend(c10::DeviceType::CUDA)->getBackendName() == "nccl";
+    } catch (const std::exception&) {                     // no backend registered for device tensors: through the host
+    }
+    Tensor gathered = fempty({world * nslab}, x), host_in, host_out;
+    if (!device_collective) {
+        host_in = at::empty({nslab}, at::TensorOptions().dtype(at::kFloat).device(at::kCPU));
+        host_out = at::empty({world * nslab}, host_in.options());
+    }
+    const fabhip_stream_t st = stream_of(x);
+    chk(fabhip_ais_phase(&a, FABHIP_AIS_INIT, 1, 0, nullptr, st), "ais_sharded_tuned (chain initialisation)");
+    int64_t n_collectives = 0;
+    for (int64_t j = 1; j <= M; ++j) {
+        chk(fabhip_ais_phase(&a, 0, (int32_t)j, (int32_t)j, slab, st), "ais_sharded_tuned (transition)");
+        if (world > 1 || device_collective) {          // (a one-rank RCCL group still runs the collective: the path a node takes)
+            if (device_collective) {
+                pg->_allgather_base(gathered, partials)->wait();
+            } else {
+                host_in.copy_(partials);
+                pg->_allgather_base(host_out, host_in)->wait();
+                gathered.copy_(host_out);
+            }
+            ++n_collectives;
+        } else {
+            gathered.copy_(partials);
+        }
+        float* pa = j == 1 ? a.p_accept_first : (j == M ? a.p_accept_last : nullptr);        // hmc.py:173-183 (store_info)
+        float* ad = j == 1 ? a.avg_distance_first : (j == M ? a.avg_distance_last : nullptr);
+        chk(fabhip_hmc_adapt_gathered(gathered.data_ptr<float>(), (int32_t)world, B, a.step_state + (j - 1), a.common_epsilon,
+                                      a.target_p_accept, 1, pa, ad, st),
+            "ais_sharded_tuned (step-size rule on the gathered slabs)");
+    }
+    chk(fabhip_ais_phase(&a, FABHIP_AIS_FINISH, 1, 0, nullptr, st), "ais_sharded_tuned (chain end)");
+    return n_collectives;
 }
 
 // Linear backward over a tape (fabhip_tape_gemm): Y / X are views INTO `tape` given as float offsets of layer 0
@@ -1619,8 +1617,8 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("create_point", create_point);
     m.impl("hmc_transition", hmc_transition);
     m.impl("metropolis_transition", metropolis_transition);
-    m.impl("ais_run", ais_run);
-    m.impl("ais_phase", ais_phase);
+    m.impl("ais_run", Plain<ais_run_impl>::op);
+    m.impl("ais_phase", Plain<ais_phase_core>::op);
     m.impl("ais_run_smc", ais_run_smc);
     m.impl("ais_phase_smc", ais_phase_smc);
     m.impl("smc_decide", smc_decide);

@@ -178,31 +178,13 @@ class HipShardBackend:
         (fabhip_metropolis_partials_floats).  Returns (Point, log_w, slab); `adapt_metropolis` applies the rule to the
         gathered slabs."""
         from .transition_operators import Metropolis
-        op, ais = self.op, self.ais
-        if not isinstance(op, Metropolis) or not ais.is_native:
+        if not isinstance(self.op, Metropolis) or not self.ais.is_native:
             raise self._ops_mod.FabhipError("exact sharded noise-scaling adaptation needs fab_torch_amd's Metropolis over a "
                                             "RealNVP flow and a native target; other plug-ins: set_eval_mode(True)")
-        if bool(op.p_target) != bool(ais.p_target) or (not ais.p_target and op.alpha != ais.alpha):
-            raise self._ops_mod.FabhipError("AIS and transition operator disagree on p_target / alpha")
-        flow, target = ais._native_parts()
-        dev = flow._nf_model.q0.loc.device
-        D, M, nu = flow.dim, self.n_transitions, int(op.n_updates)
-        f32 = dict(dtype=torch.float32, device=dev)
-        counts_stats = torch.zeros(18, **f32)
-        st = {"b": int(b), "x": torch.empty((b, D), **f32), "lq": torch.empty(b, **f32), "lp": torch.empty(b, **f32),
-              "log_w": torch.empty(b, **f32), "n_valid": counts_stats[16:18].view(torch.int32), "stats": counts_stats[:16]}
-        eps0 = torch.randn((b, D), **f32) if eps0 is None else eps0.contiguous()
-        noise_a = torch.randn((M, nu, b, D), **f32) if noise_a is None else noise_a.contiguous()
-        noise_b = torch.rand((M, nu, b), **f32) if noise_b is None else noise_b.contiguous()
-        slab = torch.empty(int(self.ops.metropolis_partials_floats(int(b), M, nu)), **f32)
-        alpha = float(ais.alpha) if ais.alpha is not None else 0.0
-        self.ops.ais_phase(*flow.native(), *target.native_target(), ais._betas(), alpha, bool(ais.p_target),
-                           self._ops_mod.TRANSITION_METROPOLIS, 3, 1, M, eps0, noise_a, noise_b, op.noise_scalings, None, None,
-                           nu, 0, 0.0, float(op.target_prob_accept), True, st["x"], st["lq"], st["lp"], None, None,
-                           st["log_w"], st["n_valid"], st["stats"], slab, None, None, None, None, None, None,
-                           self._ops_mod.precision_of(flow))
+        st = self.ais.new_phase_state(b, eps0, noise_a, noise_b, slab=True)
+        self.ais.enqueue_phase(st, 3, 1, self.n_transitions, partials=st["slab"], tune=True)
         pt, log_w = self._collect(st, grads=False)
-        return pt, log_w, slab
+        return pt, log_w, st["slab"]
 
     def adapt_metropolis(self, gathered, world, b):
         op = self.op
@@ -230,19 +212,11 @@ class HipShardBackend:
         return pt, log_w
 
     def _common(self, st):
-        ais, op = self.ais, self.op
-        flow, target = ais._native_parts()
-        alpha = float(ais.alpha) if ais.alpha is not None else 0.0
-        return (*flow.native(), *target.native_target(), ais._betas(), alpha, bool(ais.p_target),
-                self._ops_mod.TRANSITION_HMC)
+        return self.ais._call_head(*self.ais._native_parts(), self._ops_mod.TRANSITION_HMC)
 
     def _phase(self, st, phases, j0, j1, partials=None, tune=False):
-        op = self.op
-        self.ops.ais_phase(*self._common(st), int(phases), int(j0), int(j1), st["eps0"], st["noise_a"], st["noise_b"],
-                           op.epsilons, op.common_epsilon, op.mass_vector, 1, op.L, float(op.max_grad),
-                           float(op.target_p_accept), bool(tune), st["x"], st["lq"], st["lp"], st["gq"], st["gp"],
-                           st["log_w"], st["n_valid"], st["stats"], partials, None, None, None, None, None, None,
-                           self._ops_mod.precision_of(self.ais.base_distribution))
+        # (the logging slots are `adapt`'s: the step-size rule runs there, on the slabs of all ranks)
+        self.ais.enqueue_phase(st, phases, j0, j1, partials=partials, tune=tune, logging=False)
 
     def one_op_available(self, group=None) -> bool:
         """Can `ais_sharded_tuned` find this process group from C++?  (It resolves the group by NAME in c10d's registry;
@@ -285,23 +259,7 @@ class HipShardBackend:
         if not self.ais.is_native:
             raise self._ops_mod.FabhipError("sharded AIS with step-size tuning on needs a RealNVP flow and a native target "
                                             "(fabhip_ais_phase); other plug-ins: set_eval_mode(True), or tune on one rank")
-        op, ais = self.op, self.ais
-        if bool(op.p_target) != bool(ais.p_target) or (not ais.p_target and op.alpha != ais.alpha):
-            raise self._ops_mod.FabhipError("AIS and transition operator disagree on p_target / alpha")
-        flow, _ = self.ais._native_parts()
-        dev = flow._nf_model.q0.loc.device
-        D, M = flow.dim, self.n_transitions
-        f32 = dict(dtype=torch.float32, device=dev)
-        counts_stats = torch.zeros(18, **f32)                 # stats[16] | n_valid[2]: ONE device->host read at the end
-        st = {"b": int(b),
-              "eps0": (torch.randn((b, D), **f32) if eps0 is None else eps0.contiguous()),
-              "noise_a": (torch.randn((M, 1, b, D), **f32) if noise_a is None else noise_a.contiguous()),
-              "noise_b": (torch.empty((M, 1, b), **f32).exponential_(1.0) if noise_b is None else noise_b.contiguous()),
-              "x": torch.empty((b, D), **f32), "lq": torch.empty(b, **f32), "lp": torch.empty(b, **f32),
-              "gq": torch.empty((b, D), **f32), "gp": torch.empty((b, D), **f32), "log_w": torch.empty(b, **f32),
-              "n_valid": counts_stats[16:18].view(torch.int32), "stats": counts_stats[:16],
-              "slab": torch.empty(int(self.ops.hmc_partials_floats(int(b))), **f32)}
-        return st
+        return self.ais.new_phase_state(b, eps0, noise_a, noise_b, slab=True)
 
     def step(self, st, j, tune: bool = True) -> torch.Tensor:
         """Transition j with the adaptation deferred: returns this rank's acceptance slab.  `tune=False` (tuning frozen, the

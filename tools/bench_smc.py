@@ -96,13 +96,12 @@ def _phase_state(B, tau):
 def single_device_step(B, tau):
     from fab_torch_amd import _ops
     ais, be, st = _phase_state(B, tau)
-    op, ops = be.op, be.ops
+    from fab_torch_amd.ais import operator_slots
     nr = torch.rand(M, dtype=torch.float64, device=DEV)
-    args = (*be._common(st), 0, 1, 1, st["eps0"], st["noise_a"], st["noise_b"], op.epsilons, op.common_epsilon, op.mass_vector, 1,
-            op.L, float(op.max_grad), float(op.target_p_accept), False, st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"],
-            st["n_valid"], st["stats"], None, None, None, None, None, None, None, _ops.precision_of(flow), float(tau), nr, True,
-            None, None, None, None)
-    return _event_us(lambda: ops.ais_phase_smc(*args))
+    args = (*be._common(st), 0, 1, 1, st["eps0"], st["noise_a"], st["noise_b"], *operator_slots(be.op)[1][:7], False, st["x"],
+            st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], None, None, None, None, None, None,
+            None, _ops.precision_of(flow), float(tau), nr, True, None, None, None, None)
+    return _event_us(lambda: be.ops.ais_phase_smc(*args))
 
 
 def sharded_step(R, b, tau):

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench                                                                                        # noqa: E402
 import fab_torch_amd as fa                                                                          # noqa: E402
 from fab_torch_amd import _ops                                                                      # noqa: E402
+from fab_torch_amd.ais import operator_slots                                                        # noqa: E402
 
 dev = torch.device("cuda:0")
 B, D, M, L = bench.B_PER_GPU, bench.D, bench.M, bench.L
@@ -50,10 +51,10 @@ for _ in range(N):
     t = tick("target.native_target()", t)
     betas = [float(b) for b in ais.B_space]
     t = tick("betas list", t)
-    op = ais.transition_operator
-    out = ops.ais_run(*fargs, *targs, betas, float(ais.alpha), False, _ops.TRANSITION_HMC, eps0, noise_a, noise_b, op.epsilons,
-                      op.common_epsilon, op.mass_vector, 1, op.L, float(op.max_grad), float(op.target_p_accept), True,
-                      op._p_accept_first, op._p_accept_last, op._dist_first, op._dist_last, False, _ops.precision_of(fl))
+    kind, slots = operator_slots(ais.transition_operator)
+    t = tick("operator_slots", t)
+    out = ops.ais_run(*fargs, *targs, betas, ais._alpha_arg, bool(ais.p_target), kind, eps0, noise_a, noise_b, *slots, False,
+                      _ops.precision_of(fl))
     t = tick("ops.ais_run (host side)", t)
     torch.cuda.synchronize()
     t = time.perf_counter()
