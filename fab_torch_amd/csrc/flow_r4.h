@@ -53,6 +53,7 @@ struct R4Lds {
     int o_X0, o_X1, o_HA, o_HB, o_PRM, o_DP, o_PART, o_ES, o_V2, o_MASK, total;
     int o_PZ, o_BIAS;                  // fused stages (flow_r4f.h): partials of the dense narrow products, bias blocks of all layers
     int o_PF;                          // ... and 256 bytes per wave that the L2 prefetch's LDS-DMA loads land in (never read)
+    int o_PART2;                       // ... and the second partial-sum buffer of the one-barrier wide stages (see make_r4_lds)
 };
 
 FAB_HD R4Lds make_r4_lds(const FlowDims& f, bool fused = false) {
@@ -73,8 +74,18 @@ FAB_HD R4Lds make_r4_lds(const FlowDims& f, bool fused = false) {
     l.o_V2 = o; o += f.K * R4 * f.DOp;
     l.o_MASK = o; o += f.K * 2 * NTHREADS;
     l.o_PZ = l.o_BIAS = l.o_PF = 0;
+    l.o_PART2 = l.o_PART;
     if (fused) {
         o = (o + 3) & ~3;
+        // The fused wide stages (S1, S2, S4, S5 of flow_r4f.h) hand their outputs to the next stage inside the wave that
+        // consumes them (r4_epilogue_rf), so they keep ONE workgroup barrier each: partials visible.  Without the second one a
+        // wave can store the partials of stage n + 1 while another wave still reads those of stage n - hence two buffers,
+        // S1 / S4 in PART and S2 / S5 in PART2.  One barrier per stage is then sufficient: a wave stores into a buffer again
+        // two stages later, i.e. behind the barrier of the stage in between, and every wave reaches that barrier only after
+        // its own reads of the buffer (its epilogue two stages back precedes it in program order, and r4_barrier waits for
+        // the wave's LDS reads before it signals).  PZ (narrow partials) needs no second copy: its readers and its next
+        // writers are always a barrier apart (S1's z is read in front of S2's barrier and written again behind it, in S3).
+        l.o_PART2 = o; o += NWAVE * R4 * l.PN;
         l.o_PZ = o; o += 2 * NWAVE * R4 * 32;
         l.o_BIAS = o; o += (f.K + 1) * r4f_bias_stride(f.Wp);
         o = (o + 3) & ~3;
@@ -281,35 +292,65 @@ __device__ __forceinline__ void r4_epilogue(const float* __restrict__ part, int 
 
 // ---- row-fastest partials (fused stages, flow_r4f.h): PART[wave][col][row] - a lane's accumulator of a column group IS the
 // float4 (rows 0 .. 3) of its column, so the partial product goes out as G 16-byte stores instead of 4 G dword stores (and the
-// compiler does not first move 4 G accumulation registers into VGPRs).  Output o = 256 i + tid of a thread is then
-// (col = o / 4, row = o % 4); its partials still sit at part[w 4 N + o], so r4_read_partials applies unchanged.
+// compiler does not first move 4 G accumulation registers into VGPRs).  The partials of output (row, col) sit at
+// part[w 4 N + o] with o = 4 col + row.
 template <int G>
 __device__ __forceinline__ void r4_store_part_rf(const f32x4 (&acc)[G], float* __restrict__ part, const Tid4& t) {
     f32x4* pw = reinterpret_cast<f32x4*>(part + (size_t)t.wave * R4 * 64 * G) + t.lane;
 #pragma unroll
     for (int g = 0; g < G; ++g) pw[64 * g] = acc[g];
 }
+// Wave-owned outputs: lane l of wave w finishes (row = l & 3, col = 16 G w + (l >> 2) + 16 i), i < G - the 4 x 16 G block of
+// columns [16 G w, 16 G (w + 1)) that this wave's K range of the NEXT stage reads (r4f_dense_wide / r4f_narrow_mma: arow + 16 G
+// wave), so the outputs never leave the wave and the stage needs no "outputs visible" barrier.  Output o = 4 col + row =
+// 64 G w + 64 i + l; its partials sit at part[w' 4 N + o]: contiguous over the lanes, 64-dword strides between i and w', so the
+// 2 G reads come from one address register as before.  Same sums in the same order as the thread-strided mapping this
+// replaces: (P0 + P1) + (P2 + P3), then the bias.  The writes (leading dimension Wp + 16 = 16 mod 64) hit 64 different banks:
+// 16 row + (l >> 2) + const.  The ReLU sign words stay per thread (mask[tid], bit i): every wide epilogue of both directions uses
+// this mapping, so the thread that sets bit i (S1 / S2) is the one that reads it (S5 / S4).
 template <int G>
 __device__ __forceinline__ void r4_bias_rf(float (&bv)[G], const float* __restrict__ b, const Tid4& t) {
 #pragma unroll
-    for (int i = 0; i < G; ++i) bv[i] = b[(256 * i + t.tid) >> 2];
+    for (int i = 0; i < G; ++i) bv[i] = b[16 * G * t.wave + (t.lane >> 2) + 16 * i];
+}
+template <int G>
+__device__ __forceinline__ void r4_read_partials_rf(const float* part, const Tid4& t, float (&v)[G]) {
+    const unsigned addr = (unsigned)(size_t)(part + 64 * G * t.wave + t.lane);   // LDS byte address (low half of the generic pointer)
+    f32x2 r[2 * G];
+    static_for<0, G>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        r[2 * i] = lds_read2st64<i, i + 8 * G>(addr);                    // (P0, P2)
+        r[2 * i + 1] = lds_read2st64<i + 4 * G, i + 12 * G>(addr);       // (P1, P3): r[2 i] + r[2 i + 1] = (P0 + P1, P2 + P3)
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 2 * G; ++k) asm volatile("" : "+v"(r[k]));
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const f32x2 h = r[2 * i] + r[2 * i + 1];
+        v[i] = h.x + h.y;
+    }
 }
 template <int G, int EP>
 __device__ __forceinline__ void r4_epilogue_rf(const float* __restrict__ part, const float (&bv)[G], float* __restrict__ out, int ldo,
                                                unsigned* mask, const Tid4& t) {
+    static_assert(13 * G <= 256, "ds_read2st64_b32 offsets (i + 12 G at most) are 8 bits");
     unsigned m = EP == 2 ? mask[t.tid] : 0u;
     float v[G];
-    r4_read_partials<G>(part, 64 * G, t.tid, v);
-    const int row = t.tid & 3, col0 = t.tid >> 2;
+    r4_read_partials_rf<G>(part, t, v);
+    const int row = t.lane & 3, col0 = 16 * G * t.wave + (t.lane >> 2);
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         float w = v[i] + bv[i];
         if (EP == 1) { const bool pos = w > 0.f; m |= (pos ? 1u : 0u) << i; w = pos ? w : 0.f; }
         if (EP == 2) w = ((m >> i) & 1u) ? w : 0.f;
-        out[row * ldo + col0 + 64 * i] = w;
+        out[row * ldo + col0 + 16 * i] = w;
     }
     if (EP == 1) mask[t.tid] = m;
 }
+// the hand-over inside the wave: LDS executes a wave's accesses in order; the wait (and the "memory" clobber, for the
+// compiler) puts this wave's output writes in front of its own reads of them in the next stage
+__device__ __forceinline__ void r4_wave_handover() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // OUT[4][64 G] = epilogue(ACT[4][Wp] @ B)   (two workgroup barriers: partials visible / outputs visible).
 // `bv`: the bias of this thread's outputs, already in registers (r4_bias_load one W x W stage earlier).

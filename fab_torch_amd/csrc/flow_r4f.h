@@ -373,7 +373,7 @@ __device__ __forceinline__ void r4f_dense_wide(const float* act, int lda, Ring& 
     }
     r4_barrier();
     r4_epilogue_rf<G, EP>(part, bv, out, ldo, mask, t);
-    r4_barrier();
+    r4_wave_handover();                // (no second barrier: the next stage reads this wave's own columns of `out`)
 }
 
 // the same stage in FAST mode: item i = k-quads 2 i, 2 i + 1 of this wave as bf16 tiles; the activations are rounded to bf16 as
@@ -439,7 +439,7 @@ __device__ __forceinline__ void r4f_dense_wide_bf16(const float* act, int lda, R
     }
     r4_barrier();
     r4_epilogue_rf<G, EP>(part, bv, out, ldo, mask, t);
-    r4_barrier();
+    r4_wave_handover();                // (no second barrier: the next stage reads this wave's own columns of `out`)
 }
 
 // the 2 G dense tiles of items I_N, I_N + 1 against ACT[4][Wp] (this wave's K range: quads 4 G w + 2 T + sblk)
@@ -520,6 +520,7 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
     float* HB = lds + l.o_HB;
     float* DP = lds + l.o_DP;
     float* PART = lds + l.o_PART;
+    float* PART2 = lds + l.o_PART2;    // (S2 / S5; S1 / S4 use PART: make_r4_lds)
     float* PZ = lds + l.o_PZ;
     const float* BT = lds + l.o_BIAS;
     const int BS = r4f_bias_stride(f.Wp);
@@ -590,13 +591,13 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
             float zv = 0.f;                                // (read before the wide epilogue's writes: one LDS round trip less)
             if (t.tid < 128) zv = r4f_tree8(PZ, zrow, zc) + bt[2 * f.Wp + zc];
             r4_epilogue_rf<G, 1>(PART, bv, HA, l.WS, mk, t);
-            if (t.tid < 128) X[zrow * R4_DS + zc] = zv;
-            r4_barrier();
+            if (t.tid < 128) X[zrow * R4_DS + zc] = zv;    // (read next in S3: S2's barrier makes it visible)
+            r4_wave_handover();
         }
         logq += bt[2 * f.Wp + 64];
         if (tl) FAB_TL(f, 1);
-        if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART, t);
-        else r4f_dense_wide<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART, l.PN, t);
+        if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART2, t);
+        else r4f_dense_wide<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART2, l.PN, t);
         if (tl) FAB_TL(f, 3);
         {   // S3: (shift | s) = h2 W3 + b3, then AffineCoupling.inverse: z2 <- (z2 - shift) exp(-s), log_det = -sum(s)
             R4FAcc p;
@@ -672,11 +673,11 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
             for (int g = 0; g < G; ++g) bv[g] = 0.f;
             r4_barrier();
             r4_epilogue_rf<G, 2>(PART, bv, HA, l.WS, mk + NTHREADS, t);
-            r4_barrier();
+            r4_wave_handover();
         }
         if (tl) FAB_TL(f, 18);
-        if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART, t);
-        else r4f_dense_wide<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART, l.PN, t);
+        if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART2, t);
+        else r4f_dense_wide<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART2, l.PN, t);
         if (tl) FAB_TL(f, 19);
         {   // S6: g_y = dh1 W1'^T + g_z A^T, then the coupling cotangents of layer + 1
             R4FAcc p;
@@ -720,6 +721,7 @@ __device__ float flow_sample_r4f(const FlowDims& f, const R4Lds& l, const float*
     float* HA = lds + l.o_HA;
     float* HB = lds + l.o_HB;
     float* PART = lds + l.o_PART;
+    float* PART2 = lds + l.o_PART2;    // (S2 / S5; S1 / S4 use PART: make_r4_lds)
     float* PZ = lds + l.o_PZ;
     const float* BT = lds + l.o_BIAS;
     const int BS = r4f_bias_stride(f.Wp);
@@ -760,15 +762,15 @@ __device__ float flow_sample_r4f(const FlowDims& f, const R4Lds& l, const float*
         float zv = 0.f;                                // (read before the wide epilogue's writes: one LDS round trip less)
         if (t.tid < 128) zv = r4f_tree8(PZ, zrow, zc) + bt[2 * f.Wp + zc];
         r4_epilogue_rf<G, 1>(PART, bv, HA, l.WS, mk, t);
-        if (t.tid < 128) X[zrow * R4_DS + zc] = zv;
-        r4_barrier();
+        if (t.tid < 128) X[zrow * R4_DS + zc] = zv;        // (read next in S3, or by the caller: a barrier in between either way)
+        r4_wave_handover();
         logq -= -bt[2 * f.Wp + 64];
     };
 #pragma unroll 1                       // (an unrolled copy gets other ring registers, joined by copies of in-flight slots: ISA check)
     for (int v = 0; v < f.K; ++v) {
         const float* bt = BT + (size_t)v * BS;
         s1(bt);
-        r4f_dense_wide<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART, l.PN, t);
+        r4f_dense_wide<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART2, l.PN, t);
         {   // S3 + AffineCoupling.forward: z2 <- z2 exp(s) + shift, log_det = sum(s)
             R4FAcc p;
             r4f_narrow_mma<NTWM>(HB, l.WS, ring, p, t);
@@ -789,6 +791,7 @@ __device__ float flow_sample_r4f(const FlowDims& f, const R4Lds& l, const float*
         ring.next_layer();
     }
     s1(BT + (size_t)f.K * BS);
+    r4_barrier();                      // (x is read by all threads of the caller)
     ring.drain();
     *x_off = l.o_X0;
     return logq;
