@@ -6,6 +6,7 @@ loads (and, when hipcc is present and sources are newer, rebuilds) the HIP libra
 that is impossible — there is no CPU fallback."""
 from .point import Point
 from .flow import RealNVP, make_wrapped_normflow_realnvp
+from .defensive import DefensiveMixtureDistribution
 from .targets import ManyWellEnergy, GMM
 from .transition_operators import (TransitionOperator, HamiltonianMonteCarlo, Metropolis, create_point, grad_and_value,
                                    get_intermediate_log_prob, get_grad_intermediate_log_prob)
@@ -46,4 +47,5 @@ __all__ = [
     "effective_sample_size", "ess_and_log_z", "resample", "multinomial_indices", "systematic_indices",
     "multinomial_stream_indices", "multinomial_torch_compat", "gather_rows", "FABModel", "PrioritisedReplayBuffer",
     "sample_without_replacement", "PrioritisedBufferTrainer", "Trainer", "FlatAdam", "CircularCoupledRQSFlow", "make_wrapped_normflow_spline", "fast_mode",
+    "DefensiveMixtureDistribution",
 ]

@@ -89,6 +89,11 @@ class SmcArgs(C.Structure):       # fabhip_smc_args
                 ("resampled", C.c_void_p), ("ess", C.c_void_p), ("ancestors", C.c_void_p), ("log_w_pre", C.c_void_p)]
 
 
+class DefensiveArgs(C.Structure):       # fabhip_defensive_args
+    _fields_ = [("enabled", C.c_int32), ("loc", C.c_void_p), ("log_scale", C.c_void_p), ("logit", C.c_void_p),
+                ("sel", C.c_void_p)]
+
+
 # every symbol include/fabhip.h declares (checked by tests/test_cabi_and_host.py)
 SYMBOLS = [
     "fabhip_strerror", "fabhip_version", "fabhip_flow_packed_floats", "fabhip_flow_pack", "fabhip_flow_sample",
@@ -115,8 +120,9 @@ SYMBOLS = [
     "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
     "fabhip_train_step_plan", "fabhip_resample_stream_workspace_bytes", "fabhip_resample_multinomial_stream",
     "fabhip_smc_shard_workspace_bytes", "fabhip_smc_shard_pack", "fabhip_smc_shard_resample",
+    "fabhip_ais_run_mix", "fabhip_ais_phase_mix", "fabhip_defensive_log_prob",
 ]
-ABI_VERSION = 220          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 221          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -148,6 +154,9 @@ def _declare(lib):
     lib.fabhip_ais_smc_workspace_bytes.argtypes = [i64, i32, i32]
     lib.fabhip_ais_run_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), vp]
     lib.fabhip_ais_phase_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_ais_run_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), vp]
+    lib.fabhip_ais_phase_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_defensive_log_prob.argtypes = [C.POINTER(Flow), C.POINTER(DefensiveArgs), vp, vp, vp, i64, vp, vp]
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]
     lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, vp]

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _ops
+from .defensive import DefensiveMixtureDistribution
 from .flow import RealNVP
 from .point import Point
 from .targets import _NativeTarget
@@ -130,8 +131,21 @@ class AnnealedImportanceSampler:
         return torch.tensor(B_space)
 
     # ---------------------------------------------------------------------------------------------
+    def _mixture(self) -> Optional[DefensiveMixtureDistribution]:
+        """The defensive mixture this sampler draws from when the fused call applies to it (a RealNVP inside), else None."""
+        base = self.base_distribution
+        return base if isinstance(base, DefensiveMixtureDistribution) and base.is_native else None
+
+    def _refuse_mixture(self, what: str):
+        if self._mixture() is not None:
+            raise _ops.FabhipError(f"a DefensiveMixtureDistribution base is not available for {what}: the mixture runs through "
+                                   "the one-op fused call (fabhip::ais_run_mix) only")
+
     def _native_parts(self) -> Tuple[RealNVP, _NativeTarget]:
-        flow = self.base_distribution
+        """(RealNVP, native target) of the fused call; with a defensive mixture as base distribution the RealNVP inside it
+        (`_mixture()` tells the two apart: the mixture's call is ais_run_mix)."""
+        mix = self._mixture()
+        flow = mix.flow if mix is not None else self.base_distribution
         if not isinstance(flow, RealNVP):
             raise _ops.FabhipError("base_distribution must be a fab_torch_amd RealNVP for the HIP path "
                                    "(no generic / CPU fallback)")
@@ -169,8 +183,10 @@ class AnnealedImportanceSampler:
         return Point(x, lq, lp, gq, gp), log_w, n_valid, stats, base_x, base_lw
 
     def run(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None, noise_r=None,
-            trace: bool = False):
-        """(`noise_r` [M] float64: the uniforms of the resampling steps, SMC mode only; `trace`: keep the ancestors and the
+            trace: bool = False, sel=None):
+        """(`sel` [B] uniforms in [0, 1): the branch draws of a DefensiveMixtureDistribution base - chain i starts from the flow iff
+        sel_i < sigmoid(mixture_logit); absent: drawn on the device after eps0 and before the transition noise.)
+        (`noise_r` [M] float64: the uniforms of the resampling steps, SMC mode only; `trace`: keep the ancestors and the
         log-weights every decision saw in `last_smc`.)
         (`u0` [B, D]: the uniform base draws of the SPLINE flow; an error for any other base distribution.)
         Enqueue one AIS call; returns device tensors (Point fields sized [batch_size], log_w, n_valid[2],
@@ -203,10 +219,25 @@ class AnnealedImportanceSampler:
             if tau is None:
                 raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
             noise_r = check_noise_r(noise_r, M)
-        # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
-        call = ops.ais_run if tau is None else ops.ais_run_smc
-        smc = () if tau is None else (tau, noise_r, bool(trace))
-        out = call(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), *smc)
+        mix = self._mixture()
+        if sel is not None:
+            if mix is None:
+                raise _ops.FabhipError("sel (branch uniforms) belongs to a DefensiveMixtureDistribution base distribution")
+            if not torch.is_tensor(sel) or sel.dtype != torch.float32 or tuple(sel.shape) != (B,):
+                raise _ops.FabhipError(f"sel must be a float32 tensor of shape [{B}] (one uniform per chain)")
+            sel = sel.contiguous()
+        if mix is not None:
+            # defensive mixture: the same call through ais_run_mix (16-chain tiles, fp32; composes with the SMC mode)
+            mix._refuse_fast()
+            out = ops.ais_run_mix(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), tau,
+                                  noise_r, bool(trace), *mix.mix_args(), sel, True)
+            if tau is None:
+                out = out[:10]
+        else:
+            # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
+            call = ops.ais_run if tau is None else ops.ais_run_smc
+            smc = () if tau is None else (tau, noise_r, bool(trace))
+            out = call(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), *smc)
         if tau is not None:
             self.last_smc = tuple(out[10:14])
             out = out[:10]
@@ -257,6 +288,7 @@ class AnnealedImportanceSampler:
         prefetch path fills them (`normal_()` / `exponential_()`: the same draws) when the call they belong to runs, so that
         the generator is consumed in call order."""
         ops = _ops.load()
+        self._refuse_mixture("a call made in pieces (fabhip_ais_phase: sharded chains, the prefetch of repeated calls)")
         flow, _ = self._native_parts()
         kind, slots = operator_slots(self.transition_operator)
         hmc, b, D, M, n = kind == _ops.TRANSITION_HMC, int(b), flow.dim, self.n_intermediate_distributions, int(slots.n_inner)
@@ -284,6 +316,7 @@ class AnnealedImportanceSampler:
         """torch.ops.fabhip.ais_phase on a state of `new_phase_state`: the phases (FABHIP_AIS_INIT = 1, _FINISH = 2) and the
         transitions j0 .. j1 of this sampler's call.  `tune` overrides the operator's own setting (with `partials` the
         adaptation is deferred to the caller); `logging=False`: the operator's logging slots are left alone."""
+        self._refuse_mixture("a call made in pieces (fabhip_ais_phase: sharded chains, the prefetch of repeated calls)")
         flow, target = self._native_parts()
         kind, s = operator_slots(self.transition_operator)
         log = s[8:] if logging else (None, None, None, None)
@@ -349,6 +382,14 @@ class AnnealedImportanceSampler:
 
     @property
     def is_native(self) -> bool:
+        if self._mixture() is not None:
+            # the fused call evaluates the mixture itself; the operator (whose own `is_native` speaks of a plain RealNVP: stepped
+            # from Python it evaluates the mixture through the plug-in) only has to be this package's, over the same plug-ins
+            op = self.transition_operator
+            return _owner_or_none(self.target_log_prob, _NativeTarget) is not None and \
+                isinstance(op, (HamiltonianMonteCarlo, Metropolis)) and \
+                _owner_or_none(op.base_log_prob, DefensiveMixtureDistribution) is self.base_distribution and \
+                _owner_or_none(op.target_log_prob, _NativeTarget) is not None
         return isinstance(self.base_distribution, RealNVP) and \
             _owner_or_none(self.target_log_prob, _NativeTarget) is not None and self.transition_operator.is_native
 
@@ -442,9 +483,12 @@ class AnnealedImportanceSampler:
             self.__dict__["_smc_info"] = {"n_resampled": int(h[0]), "ess_min_in_chain": float(h[1])}
 
     def sample_and_log_weights(self, batch_size: int, logging: bool = True, eps0=None, noise_a=None, noise_b=None,
-                               u0=None, noise_r=None) -> Tuple[Point, torch.Tensor]:
+                               u0=None, noise_r=None, sel=None) -> Tuple[Point, torch.Tensor]:
         fused_spline = self._spline_parts() is not None
         smc_on = self.resample_threshold is not None
+        mix_on = self._mixture() is not None and self.is_native
+        if sel is not None and not mix_on:
+            raise _ops.FabhipError("sel (branch uniforms) belongs to the fused call over a DefensiveMixtureDistribution base")
         if fused_spline:
             self._refuse_resampling("the fused spline-flow call")
         if noise_r is not None and not smc_on:
@@ -458,8 +502,8 @@ class AnnealedImportanceSampler:
                                        "draws its own samples in sample_and_log_prob")
             return self._sample_generic(batch_size, logging, noise_a, noise_b, noise_r=noise_r)
         repeated = None
-        # (SMC mode: the prefetch of repeated calls is bypassed - its second piece runs through the plain phase op)
-        if (not fused_spline and not smc_on and self.prefetch and eps0 is None and noise_a is None and noise_b is None
+        # (SMC mode, defensive mixture: the prefetch of repeated calls is bypassed - its pieces run through the plain phase op)
+        if (not fused_spline and not smc_on and not mix_on and self.prefetch and eps0 is None and noise_a is None and noise_b is None
                 and isinstance(self.transition_operator, HamiltonianMonteCarlo)):
             flow, target = self._native_parts()
             flow.native()                                                        # (the image - and its key - of the current parameters)
@@ -478,7 +522,7 @@ class AnnealedImportanceSampler:
                 if smc_on:
                     self._pf_take(None)                                          # (a piece prefetched before the mode was set)
                     self.__dict__.pop("_pf_last_key", None)
-                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b, noise_r=noise_r)
+                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b, noise_r=noise_r, sel=sel)
             host, (n_init, n_end) = _ops.read_counts_and_stats(n_valid, stats)   # the single device->host read
         if n_init == 0:
             raise NoValidPoints("init")

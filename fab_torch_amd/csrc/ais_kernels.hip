@@ -13,6 +13,7 @@
 #include "flow_r4f.h"
 #include "flow_r8.h"
 #include "launch.h"
+#include "defensive_device.h"
 
 #pragma clang fp contract(off)   // keep a*b+c un-fused in the elementwise code, like the eager CPU reference
 
@@ -57,15 +58,19 @@ __device__ __forceinline__ float clamp_nan0(float g, float mg) {
 // ------------------------------------------------------------------------------------------------
 // create_point: log q (+grad), log p (+grad) at point.x      (fab/sampling_methods/base.py:59-72)
 // ------------------------------------------------------------------------------------------------
-template <int NTWM, bool GRAD, bool FAST>
+// MIX: the defensive mixture's density (+ gradient) alone, for fabhip_defensive_log_prob: no target is evaluated, pt.lp / pt.gp
+// are not written (the fused call creates its points in ais_init_body / hmc_step_body / metropolis_body).
+template <int NTWM, bool GRAD, bool FAST, bool MIX = false>
 __device__ __forceinline__ void create_point_body(const FlowDims& f, const FlowLds& l, const ExtraLds& x,
                                                   const float* __restrict__ packed, const TargetDev& tg, const PointDev& pt,
-                                                  long B, float* lds) {
+                                                  long B, float* lds, const MixDev& mx = MixDev{}) {
     Tid t;
     const int D = f.D;
     const long row0 = (long)blockIdx.x * ROWS;
     float* XP = lds + x.o_XP;
     float* GP = lds + x.o_GP;
+    float* MP = lds + x.total;                               // MIX: the staged mixture parameters, behind the plan
+    if constexpr (MIX) mix_stage(mx, D, MP, t);
     zero_dp(l, lds, t);
     for (int e = t.tid; e < ROWS * D; e += NTHREADS) {
         const long g = row0 + e / D;
@@ -75,7 +80,16 @@ __device__ __forceinline__ void create_point_body(const FlowDims& f, const FlowL
     load_state_to_u0(l, D, lds, XP, t);
     __syncthreads();
     int goff = 0;
-    const float lq = flow_log_prob_tile<NTWM, GRAD, false, FAST>(f, l, packed, lds, t, &goff);
+    float lq = flow_log_prob_tile<NTWM, GRAD, false, FAST>(f, l, packed, lds, t, &goff);
+    if constexpr (MIX) {
+        lq = mix_tile<GRAD>(MP, D, XP, D, lds + goff, l.DS, lq, t);
+        const long g = row0 + t.row;
+        if (g < B) {
+            if (t.c == 0) pt.lq[g] = lq;
+            if (GRAD) for (int j = t.c; j < D; j += 16) pt.gq[g * D + j] = lds[goff + t.row * l.DS + j];
+        }
+        return;
+    }
     const float lp = target_tile<GRAD>(tg, XP, D, GP, D, t);
     const long g = row0 + t.row;
     if (g < B) {
@@ -95,6 +109,12 @@ __global__ __launch_bounds__(NTHREADS) void k_create_point(FlowDims f, FlowLds l
     extern __shared__ __attribute__((aligned(16))) float lds[];
     create_point_body<NTWM, GRAD, false>(f, l, x, packed, tg, pt, B, lds);
 }
+template <int NTWM, bool GRAD>
+__global__ __launch_bounds__(NTHREADS) void k_create_point_mix(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
+                                                               PointDev pt, long B, MixDev mx) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    create_point_body<NTWM, GRAD, false, true>(f, l, x, packed, TargetDev{}, pt, B, lds, mx);
+}
 // fast mode (bf16 W x W GEMMs, flow_device.h): same kernel, not the parity path
 template <int NTWM, bool GRAD>
 __global__ __launch_bounds__(NTHREADS) void k_create_point_fast(FlowDims f, FlowLds l, ExtraLds x,
@@ -109,16 +129,22 @@ __global__ __launch_bounds__(NTHREADS) void k_create_point_fast(FlowDims f, Flow
 // log_w = pi_beta1(point) - log_q0.   With GRAD (HMC) log q is re-evaluated through log_prob, as the
 // reference does (base.py:65-68 ignores the supplied log_q_x).
 // ------------------------------------------------------------------------------------------------
-template <int NTWM, bool GRAD, bool FAST>
+// MIX (defensive mixture, defensive_device.h): the whole tile runs the flow's sampler, then row i keeps the flow's x iff
+// sel[i] < sigmoid(logit) and takes loc + exp(log_scale) eps0[i] otherwise; log q0 is the mixture density at x from the density
+// direction (the reference's sample_and_log_prob is log_prob(sample())), so the density pass runs for Metropolis too.
+template <int NTWM, bool GRAD, bool FAST, bool MIX = false>
 __device__ __forceinline__ void ais_init_body(const FlowDims& f, const FlowLds& l, const ExtraLds& x,
                                               const float* __restrict__ packed, const TargetDev& tg,
                                               const float* __restrict__ eps0, const PointDev& pt, float* __restrict__ log_w,
-                                              float* __restrict__ base_log_w, const fabhip_anneal& an, long B, float* lds) {
+                                              float* __restrict__ base_log_w, const fabhip_anneal& an, long B, float* lds,
+                                              const MixDev& mx = MixDev{}, const float* __restrict__ sel = nullptr) {
     Tid t;
     const int D = f.D;
     const long row0 = (long)blockIdx.x * ROWS;
     float* XP = lds + x.o_XP;
     float* GP = lds + x.o_GP;
+    float* MP = lds + x.total;
+    if constexpr (MIX) mix_stage(mx, D, MP, t);
     zero_dp(l, lds, t);
     for (int e = t.tid; e < ROWS * l.DS; e += NTHREADS) {
         const int r = e / l.DS, j = e % l.DS;
@@ -127,15 +153,26 @@ __device__ __forceinline__ void ais_init_body(const FlowDims& f, const FlowLds& 
     }
     __syncthreads();
     int xoff = 0;
-    const float lq0 = flow_sample_tile<NTWM>(f, l, packed, lds, t, &xoff);
-    for (int j = t.c; j < D; j += 16) XP[t.row * D + j] = lds[xoff + t.row * l.DS + j];
+    float lq0 = flow_sample_tile<NTWM>(f, l, packed, lds, t, &xoff);
+    if constexpr (MIX) {
+        const long gr = row0 + t.row;
+        const bool from_flow = gr < B ? sel[gr] < MP[4 * D + 2] : true;
+        for (int j = t.c; j < D; j += 16)
+            XP[t.row * D + j] = from_flow ? lds[xoff + t.row * l.DS + j] : MP[j] + expf(MP[D + j]) * eps0[gr * D + j];
+    } else {
+        for (int j = t.c; j < D; j += 16) XP[t.row * D + j] = lds[xoff + t.row * l.DS + j];
+    }
     __syncthreads();
     float lq = lq0;
     int goff = 0;
-    if (GRAD) {
+    if (GRAD || MIX) {
         load_state_to_u0(l, D, lds, XP, t);
         __syncthreads();
-        lq = flow_log_prob_tile<NTWM, true, false, FAST>(f, l, packed, lds, t, &goff);
+        lq = flow_log_prob_tile<NTWM, GRAD, false, FAST>(f, l, packed, lds, t, &goff);
+        if constexpr (MIX) {
+            lq = mix_tile<GRAD>(MP, D, XP, D, lds + goff, l.DS, lq, t);
+            lq0 = lq;
+        }
     }
     const float lp = target_tile<GRAD>(tg, XP, D, GP, D, t);
     const long g = row0 + t.row;
@@ -163,6 +200,14 @@ __global__ __launch_bounds__(NTHREADS) void k_ais_init(FlowDims f, FlowLds l, Ex
                                                        fabhip_anneal an, long B) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     ais_init_body<NTWM, GRAD, false>(f, l, x, packed, tg, eps0, pt, log_w, base_log_w, an, B, lds);
+}
+template <int NTWM, bool GRAD>
+__global__ __launch_bounds__(NTHREADS) void k_ais_init_mix(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
+                                                           TargetDev tg, const float* __restrict__ eps0, PointDev pt,
+                                                           float* __restrict__ log_w, float* __restrict__ base_log_w,
+                                                           fabhip_anneal an, long B, MixDev mx, const float* __restrict__ sel) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    ais_init_body<NTWM, GRAD, false, true>(f, l, x, packed, tg, eps0, pt, log_w, base_log_w, an, B, lds, mx, sel);
 }
 // fast mode: the sampling pass stays fp32; the density the transitions continue from is the bf16-GEMM one
 template <int NTWM>
@@ -255,10 +300,10 @@ __device__ __forceinline__ void hmc_adapt_last(const HmcK& a, float* scratch, in
     }
 }
 
-template <int NTWM, bool FAST>
+template <int NTWM, bool FAST, bool MIX = false>
 __device__ __forceinline__ void hmc_step_body(const FlowDims& f, const FlowLds& l, const ExtraLds& x,
                                               const float* __restrict__ packed, const TargetDev& tg, const HmcK& a,
-                                              float* lds) {
+                                              float* lds, const MixDev& mx = MixDev{}) {
     Tid t;
     const int D = f.D;
     const long nv = a.n_valid ? (long)*a.n_valid : a.B;
@@ -275,6 +320,7 @@ __device__ __forceinline__ void hmc_step_body(const FlowDims& f, const FlowLds& 
     const long g = row0 + t.row;
     const bool active = g < nv;
     const float eps = *a.eps_ptr + *a.ceps_ptr;                     // get_epsilon (hmc.py:90-100)
+    if constexpr (MIX) mix_stage(mx, D, lds + x.total, t);          // (read behind the barriers of the first leapfrog)
     zero_dp(l, lds, t);
     float k0 = 0.f;
     for (int j = t.c; j < D; j += 16) {
@@ -306,6 +352,7 @@ __device__ __forceinline__ void hmc_step_body(const FlowDims& f, const FlowLds& 
         load_state_to_u0(l, D, lds, XP, t);
         __syncthreads();
         lq = flow_log_prob_tile<NTWM, true, false, FAST>(f, l, packed, lds, t, &goff);
+        if constexpr (MIX) lq = mix_tile<true>(lds + x.total, D, XP, D, lds + goff, l.DS, lq, t);
         lp = target_tile<true>(tg, XP, D, GP, D, t);
         for (int j = t.c; j < D; j += 16) {
             const float gr = -(a.c.g_q * lds[goff + t.row * l.DS + j] + a.c.g_p * GP[t.row * D + j]);
@@ -371,6 +418,12 @@ __global__ __launch_bounds__(NTHREADS) void k_hmc_step(FlowDims f, FlowLds l, Ex
                                                        TargetDev tg, HmcK a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     hmc_step_body<NTWM, false>(f, l, x, packed, tg, a, lds);
+}
+template <int NTWM>
+__global__ __launch_bounds__(NTHREADS) void k_hmc_step_mix(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
+                                                           TargetDev tg, HmcK a, MixDev mx) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    hmc_step_body<NTWM, false, true>(f, l, x, packed, tg, a, lds, mx);
 }
 // fast mode (fabhip_set_fast_mode): the W x W GEMMs of every coupling layer on the bf16 matrix cores
 template <int NTWM>
@@ -877,10 +930,10 @@ struct MetK {
     int nblk;
 };
 
-template <int NTWM>
-__global__ __launch_bounds__(NTHREADS) void k_metropolis(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
-                                                         TargetDev tg, MetK a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+template <int NTWM, bool MIX>
+__device__ __forceinline__ void metropolis_body(const FlowDims& f, const FlowLds& l, const ExtraLds& x,
+                                                const float* __restrict__ packed, const TargetDev& tg, const MetK& a,
+                                                float* lds, const MixDev& mx = MixDev{}) {
     Tid t;
     const int D = f.D;
     const long nv = a.n_valid ? (long)*a.n_valid : a.B;
@@ -895,6 +948,7 @@ __global__ __launch_bounds__(NTHREADS) void k_metropolis(FlowDims f, FlowLds l, 
     float* ROWB = lds + x.o_ROW;
     const long g = row0 + t.row;
     const bool active = g < nv;
+    if constexpr (MIX) mix_stage(mx, D, lds + x.total, t);
     zero_dp(l, lds, t);
     for (int j = t.c; j < D; j += 16) XC[t.row * D + j] = active ? a.cur.x[g * D + j] : 0.f;
     float lq_c = 0.f, lp_c = 0.f;
@@ -911,7 +965,8 @@ __global__ __launch_bounds__(NTHREADS) void k_metropolis(FlowDims f, FlowLds l, 
         load_state_to_u0(l, D, lds, XN, t);
         __syncthreads();
         int goff;
-        const float lq = flow_log_prob_tile<NTWM, false>(f, l, packed, lds, t, &goff);
+        float lq = flow_log_prob_tile<NTWM, false>(f, l, packed, lds, t, &goff);
+        if constexpr (MIX) lq = mix_tile<false>(lds + x.total, D, XN, D, nullptr, 0, lq, t);
         const float lp = target_tile<false>(tg, XN, D, GP, D, t);
         float acc = expf((a.c.c_q * lq + a.c.c_p * lp) - prev_lp);
         if (!isfinite(acc)) acc = 0.f;                          // nan_to_num(nan=0, posinf=0, neginf=0)
@@ -941,6 +996,19 @@ __global__ __launch_bounds__(NTHREADS) void k_metropolis(FlowDims f, FlowLds l, 
             a.log_w[g] = a.log_w[g] + (num - den);
         }
     }
+}
+
+template <int NTWM>
+__global__ __launch_bounds__(NTHREADS) void k_metropolis(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
+                                                         TargetDev tg, MetK a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    metropolis_body<NTWM, false>(f, l, x, packed, tg, a, lds);
+}
+template <int NTWM>
+__global__ __launch_bounds__(NTHREADS) void k_metropolis_mix(FlowDims f, FlowLds l, ExtraLds x, const float* __restrict__ packed,
+                                                             TargetDev tg, MetK a, MixDev mx) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    metropolis_body<NTWM, true>(f, l, x, packed, tg, a, lds, mx);
 }
 
 __global__ void k_metropolis_adapt(const float* __restrict__ part_acc, int nblk, int n_updates, const int* n_valid,
@@ -1311,6 +1379,55 @@ static int launch_hmc_step(const FlowDims& f, const float* packed, const TargetD
     return check_launch();
 }
 
+// ---- defensive mixture (defensive_device.h): the 16-chain kernels' *_mix instantiations, fp32 only ----------------------------
+template <int NTWM>
+static int launch_create_point_mix(const FlowDims& f, const float* packed, const PointDev& pt, int with_grad, long B,
+                                   const MixDev& mx, hipStream_t st) {
+    const FlowLds l = make_flow_lds(f, with_grad != 0);
+    const ExtraLds x = make_extra_lds(l, f.D);
+    const size_t bytes = (size_t)(x.total + mix_lds_floats(f.D)) * 4;
+    const dim3 grid(nblk_of(B)), block(NTHREADS);
+    if (with_grad) {
+        FAB_TRY(set_max_lds((const void*)k_create_point_mix<NTWM, true>, bytes));
+        hipLaunchKernelGGL((k_create_point_mix<NTWM, true>), grid, block, bytes, st, f, l, x, packed, pt, B, mx);
+    } else {
+        FAB_TRY(set_max_lds((const void*)k_create_point_mix<NTWM, false>, bytes));
+        hipLaunchKernelGGL((k_create_point_mix<NTWM, false>), grid, block, bytes, st, f, l, x, packed, pt, B, mx);
+    }
+    return check_launch();
+}
+
+template <int NTWM>
+static int launch_ais_init_mix(const FlowDims& f, const float* packed, const TargetDev& tg, const float* eps0,
+                               const PointDev& pt, float* log_w, float* base_log_w, fabhip_anneal an, int with_grad, long B,
+                               const MixDev& mx, const float* sel, hipStream_t st) {
+    const FlowLds l = make_flow_lds(f, with_grad != 0);
+    const ExtraLds x = make_extra_lds(l, f.D);
+    const size_t bytes = (size_t)(x.total + mix_lds_floats(f.D)) * 4;
+    const dim3 grid(nblk_of(B)), block(NTHREADS);
+    if (with_grad) {
+        FAB_TRY(set_max_lds((const void*)k_ais_init_mix<NTWM, true>, bytes));
+        hipLaunchKernelGGL((k_ais_init_mix<NTWM, true>), grid, block, bytes, st, f, l, x, packed, tg, eps0, pt, log_w, base_log_w,
+                           an, B, mx, sel);
+    } else {
+        FAB_TRY(set_max_lds((const void*)k_ais_init_mix<NTWM, false>, bytes));
+        hipLaunchKernelGGL((k_ais_init_mix<NTWM, false>), grid, block, bytes, st, f, l, x, packed, tg, eps0, pt, log_w, base_log_w,
+                           an, B, mx, sel);
+    }
+    return check_launch();
+}
+
+template <int NTWM>
+static int launch_hmc_step_mix(const FlowDims& f, const float* packed, const TargetDev& tg, const HmcK& a, const MixDev& mx,
+                               hipStream_t st) {
+    const FlowLds l = make_flow_lds(f, true);
+    const ExtraLds x = make_extra_lds(l, f.D);
+    const size_t bytes = (size_t)(x.total + mix_lds_floats(f.D)) * 4;
+    FAB_TRY(set_max_lds((const void*)k_hmc_step_mix<NTWM>, bytes));
+    hipLaunchKernelGGL((k_hmc_step_mix<NTWM>), dim3(nblk_of(a.B)), dim3(NTHREADS), bytes, st, f, l, x, packed, tg, a, mx);
+    return check_launch();
+}
+
 // 4-chain tiles pay when 16-chain tiles cannot fill the chip: up to 288 workgroups of 4 chains (B <= 1152); off in fast
 // mode (no bf16 variant of the 4-chain kernel).  FABHIP_OPT_TILE_SHAPE = 16 / 4 forces the choice (tests exercise both).
 // Shapes: D <= 32 and hidden width <= 320 only - the D > 32 and the 512-wide instantiations of the 4-chain kernel spill
@@ -1459,7 +1576,19 @@ static int launch_metropolis(const FlowDims& f, const float* packed, const Targe
     return check_launch();
 }
 
-static int hmc_transition_impl(const fabhip_hmc_args* a, hipStream_t st, int* ticket = nullptr) {
+template <int NTWM>
+static int launch_metropolis_mix(const FlowDims& f, const float* packed, const TargetDev& tg, const MetK& a, const MixDev& mx,
+                                 hipStream_t st) {
+    const FlowLds l = make_flow_lds(f, false);
+    const ExtraLds x = make_extra_lds(l, f.D);
+    const size_t bytes = (size_t)(x.total + mix_lds_floats(f.D)) * 4;
+    FAB_TRY(set_max_lds((const void*)k_metropolis_mix<NTWM>, bytes));
+    hipLaunchKernelGGL((k_metropolis_mix<NTWM>), dim3(a.nblk), dim3(NTHREADS), bytes, st, f, l, x, packed, tg, a, mx);
+    return check_launch();
+}
+
+// `mx.on`: the defensive mixture - 16-chain tiles at every batch size, the step-size rule in k_hmc_adapt
+static int hmc_transition_impl(const fabhip_hmc_args* a, hipStream_t st, int* ticket = nullptr, const MixDev& mx = MixDev{}) {
     const FlowDims f = flow_dims_of(a->flow);
     const TargetDev tg = make_target_dev(a->target);
     const int D = f.D;
@@ -1471,8 +1600,8 @@ static int hmc_transition_impl(const fabhip_hmc_args* a, hipStream_t st, int* ti
     float* part_dist = (float*)ws; ws += align256((size_t)nblk * 4);
     float* row_acc = (float*)ws; ws += align256((size_t)nblk * ROWS * 4);
     float* row_dist = (float*)ws; ws += align256((size_t)nblk * ROWS * 4);
-    const bool r8 = use_r8_tiles(f, a->B);
-    const bool r4 = !r8 && use_r4_tiles(f, a->B);
+    const bool r8 = !mx.on && use_r8_tiles(f, a->B);
+    const bool r4 = !mx.on && !r8 && use_r4_tiles(f, a->B);
     PointDev prop{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (a->n_outer > 1) {
         float* pb = (float*)ws;
@@ -1497,7 +1626,8 @@ static int hmc_transition_impl(const fabhip_hmc_args* a, hipStream_t st, int* ti
         k.ticket = fold ? ticket : nullptr;
         k.eps_w = a->epsilons + n; k.ceps_w = a->common_epsilon; k.target_p_accept = a->target_p_accept; k.tune = a->tune;
         k.p_accept_out = a->p_accept ? a->p_accept + n : nullptr; k.dist_out = a->avg_distance; k.nblk = nblk;
-        if (r8) FAB_TRY(launch_hmc_step_r8(f, a->flow.packed, tg, k, st));
+        if (mx.on) FAB_DISPATCH_NTW_NORET(f, launch_hmc_step_mix, f, a->flow.packed, tg, k, mx, st);
+        else if (r8) FAB_TRY(launch_hmc_step_r8(f, a->flow.packed, tg, k, st));
         else if (r4) FAB_DISPATCH_NTW_NORET(f, launch_hmc_step_r4, f, a->flow.packed, tg, k, st);
         else FAB_DISPATCH_NTW_NORET(f, launch_hmc_step, f, a->flow.packed, tg, k, st);
         if (fold) { FAB_TRY(check_launch()); continue; }
@@ -1510,7 +1640,8 @@ static int hmc_transition_impl(const fabhip_hmc_args* a, hipStream_t st, int* ti
     return FABHIP_OK;
 }
 
-static int metropolis_transition_impl(const fabhip_metropolis_args* a, hipStream_t st, float* partials = nullptr) {
+static int metropolis_transition_impl(const fabhip_metropolis_args* a, hipStream_t st, float* partials = nullptr,
+                                      const MixDev& mx = MixDev{}) {
     const FlowDims f = flow_dims_of(a->flow);
     const TargetDev tg = make_target_dev(a->target);
     const int nblk = nblk_of(a->B);
@@ -1519,7 +1650,8 @@ static int metropolis_transition_impl(const fabhip_metropolis_args* a, hipStream
     k.cur = make_point_dev(a->point); k.B = a->B; k.n_valid = a->n_valid; k.c = a->cur; k.nx = a->next;
     k.log_w = a->log_w; k.noise_x = a->noise_x; k.noise_u = a->noise_u; k.scalings = a->noise_scalings;
     k.n_updates = a->n_updates; k.part_acc = partials ? partials : (float*)a->workspace; k.nblk = nblk;
-    FAB_DISPATCH_NTW_NORET(f, launch_metropolis, f, a->flow.packed, tg, k, st);
+    if (mx.on) FAB_DISPATCH_NTW_NORET(f, launch_metropolis_mix, f, a->flow.packed, tg, k, mx, st);
+    else FAB_DISPATCH_NTW_NORET(f, launch_metropolis, f, a->flow.packed, tg, k, st);
     if (partials) {                  // deferred rule (sharded chains): [n_updates][nblk] block sums | chains in use
         hipLaunchKernelGGL(k_metropolis_count, dim3(1), dim3(1), 0, st, a->n_valid, (long)a->B,
                            partials + (size_t)a->n_updates * nblk);
@@ -1870,6 +2002,31 @@ int fabhip_ais_run_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, fab
 
 int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin, int32_t j_end,
                          float* partials, fabhip_stream_t stream) {
+    return fabhip_ais_phase_mix(a, smc, nullptr, phases, j_begin, j_end, partials, stream);
+}
+
+int fabhip_ais_run_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                       fabhip_stream_t stream) {
+    if (!a) return FABHIP_EINVAL;
+    return fabhip_ais_phase_mix(a, smc, mix, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+}
+
+int fabhip_defensive_log_prob(const fabhip_flow* flow, const fabhip_defensive_args* mix, const float* x, float* log_q,
+                              float* grad_x, int64_t B, void* workspace, fabhip_stream_t stream) {
+    (void)workspace;
+    if (!flow || !flow->packed || !mix || !mix->enabled || !x || !log_q || B < 0) return FABHIP_EINVAL;
+    FAB_TRY(check_flow_shape(flow->dim, flow->n_layers, flow->width));
+    FAB_TRY(check_mix(mix));
+    if (B == 0) return FABHIP_OK;
+    const FlowDims f = flow_dims_of(*flow);
+    if (f.fast) return FABHIP_ENOTSUP;                                // (no bf16 instantiation of the mixture kernels)
+    const PointDev pt{const_cast<float*>(x), log_q, nullptr, grad_x, nullptr};
+    FAB_DISPATCH_NTW(f, launch_create_point_mix, f, flow->packed, pt, grad_x ? 1 : 0, (long)B, make_mix_dev(mix),
+                     (hipStream_t)stream);
+}
+
+int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix, int32_t phases,
+                         int32_t j_begin, int32_t j_end, float* partials, fabhip_stream_t stream) {
     if (!a || !a->flow.packed || !a->betas || !a->step_state || !a->log_w ||
         !a->n_valid || !a->stats || !a->workspace || a->B < 1 || a->M < 1 || a->n_inner < 1)
         return FABHIP_EINVAL;
@@ -1886,6 +2043,10 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
     FAB_TRY(check_target(&a->target, a->flow.dim));
     FAB_TRY(check_point(a->point, hmc));
     const bool smc_on = smc && smc->enabled != 0;
+    FAB_TRY(check_mix(mix));
+    const MixDev mx = make_mix_dev(mix);
+    if (mx.on && (partials || resolve_fast(a->flow.precision))) return FABHIP_ENOTSUP;    // (sharded chains, bf16 fast mode)
+    if (mx.on && do_init && !mix->sel) return FABHIP_EINVAL;                              // (like eps0: read by INIT only)
     if (smc_on && partials) return FABHIP_ENOTSUP;
     if (smc_on && j_begin <= j_end && !smc->u) return FABHIP_EINVAL;                  // (like the noise: read by the transitions only)
     if (a->workspace_bytes < (smc_on ? fabhip_ais_smc_workspace_bytes(a->B, a->flow.dim, a->n_inner)
@@ -1909,7 +2070,7 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
     const size_t ess_bytes = fabhip_ess_workspace_bytes(B);
     // step-size rule inside the transition kernels (hmc_adapt_last): only where the ticket word is known to be zero (this call's or,
     // with FABHIP_AIS_CONTINUE, an earlier call's init phase zeroed it; every transition kernel leaves it zero)
-    int* ticket = (hmc && !partials && option(FABHIP_OPT_ADAPT_FOLD) != 0 && nblk_of(B) <= 2048 &&
+    int* ticket = (hmc && !mx.on && !partials && option(FABHIP_OPT_ADAPT_FOLD) != 0 && nblk_of(B) <= 2048 &&
                    (use_r8_tiles(f, B) || use_r4_tiles(f, B))) ? (int*)ws : nullptr;      // (2 nblk floats of LDS scratch)
     // (round 6: a call that runs transitions on a workspace nobody zeroed - the second piece of a call whose INIT piece was its own
     //  fabhip_ais_phase call, fab_torch_amd/ais.py: repeated calls - zeroes the word itself: one 4-byte fill instead of a
@@ -1936,7 +2097,10 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
     fabhip_anneal_coefs(a->betas[1], a->alpha, a->p_target, &a1);
     {
         const PointDev pt = make_point_dev(a->point);
-        if (hmc && use_r8_tiles(f, B)) {
+        if (mx.on) {
+            FAB_DISPATCH_NTW_NORET(f, launch_ais_init_mix, f, a->flow.packed, tg, a->eps0, pt, a->log_w, a->base_log_w, a1,
+                                   hmc ? 1 : 0, B, mx, mix->sel, st);
+        } else if (hmc && use_r8_tiles(f, B)) {
             FAB_TRY(fabhip_flow_sample(&a->flow, a->eps0, a->point.x, lwb, B, stream));
             FAB_TRY(launch_ais_init_r8(f, a->flow.packed, tg, lwb, pt, a->log_w, a->base_log_w, a1, B, st));
         } else if (hmc && use_r4_tiles(f, B) && option(FABHIP_OPT_R4_STREAM) != 0) {
@@ -2000,7 +2164,7 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
             // logging slots of the first / last distribution (hmc.py:173-183), one acceptance per outer loop
             if (j == 1) { h.p_accept = a->p_accept_first; h.avg_distance = a->avg_distance_first; }
             else if (j == a->M) { h.p_accept = a->p_accept_last; h.avg_distance = a->avg_distance_last; }
-            FAB_TRY(hmc_transition_impl(&h, st, ticket));
+            FAB_TRY(hmc_transition_impl(&h, st, ticket, mx));
         } else {
             fabhip_metropolis_args m;
             m.flow = a->flow; m.target = a->target; m.point = a->point; m.B = B; m.n_valid = a->n_valid;
@@ -2011,7 +2175,7 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, i
             m.workspace = trans_ws; m.workspace_bytes = tws;
             // deferred rule: transition j's block sums + count at slab offset (j - 1) (n_updates nblk + 1)
             FAB_TRY(metropolis_transition_impl(&m, st, partials ? partials + (size_t)(j - 1) * ((size_t)a->n_inner * nblk_of(B) + 1)
-                                                                 : nullptr));
+                                                                 : nullptr, mx));
         }
     }
     // 5. remove nan/inf ("chain end"), 6. ESS / log Z over the survivors (ais.py:77-86)

@@ -920,6 +920,13 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
     a.workspace = aligned(c.ws); a.workspace_bytes = nb;
 }
 
+// Defensive-mixture base distribution of the AIS ops (fabhip_defensive_args): the module's three parameter tensors as they are
+// (the kernels read them; no copy, no host read) and the branch uniforms `sel` [B] (absent: drawn from the default generator).
+struct MixOp {
+    bool enabled = true;
+    Tensor loc, log_scale, logit;
+    optional<Tensor> sel;
+};
 // SMC mode of the AIS ops (fabhip_smc_args): `tau` absent = the plain call through the same entry points.  noise_r [M] float64
 // (absent: drawn from the default generator AFTER the transition noise); the per-transition records are allocated here.
 struct SmcOp {
@@ -927,7 +934,16 @@ struct SmcOp {
     optional<Tensor> noise_r;
     bool want_trace = false;
     Tensor resampled, ess, ancestors, log_w_pre, u;     // out (ais_run_smc)
+    const MixOp* mix = nullptr;                         // ais_run_mix: the call goes through fabhip_ais_*_mix
 };
+
+fabhip_defensive_args make_mix(const MixOp& m, int64_t dim, const Tensor& ref) {
+    fabhip_defensive_args d = {};
+    d.enabled = m.enabled ? 1 : 0;
+    d.loc = fpn(m.loc, dim, ref, "loc"); d.log_scale = fpn(m.log_scale, dim, ref, "log_scale");
+    d.logit = fpn(m.logit, 1, ref, "mixture_logit");
+    return d;
+}
 
 static Tensor smc_uniforms(const optional<Tensor>& noise_r, int64_t M, const Tensor& like) {
     if (!noise_r.has_value()) return at::rand({M}, like.options().dtype(at::kDouble));
@@ -1005,17 +1021,32 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     };
     const fabhip_smc_args* sap = smc != nullptr ? &sa : nullptr;
     const fabhip_stream_t st = stream_of(eps0);
+    // defensive mixture (ais_run_mix): the same entry points with a non-NULL fabhip_defensive_args; `sel` absent: drawn after eps0
+    // (the caller's draw) and before the transition noise
+    fabhip_defensive_args ma = {};
+    const fabhip_defensive_args* map = nullptr;
+    Tensor sel;
+    if (smc != nullptr && smc->mix != nullptr) {
+        ma = make_mix(*smc->mix, dim, eps0);
+        if (smc->mix->enabled) {
+            sel = smc->mix->sel.has_value() ? *smc->mix->sel : at::rand({B}, eps0.options());
+            ma.sel = fpn(sel, B, eps0, "sel");
+        }
+        map = &ma;
+    }
+    const char* what = map ? "ais_run_mix" : "ais_run";
     if (!draw_inside) {
         smc_outputs();
-        chk(fabhip_ais_run_smc(&a, sap, st), "ais_run");
+        chk(fabhip_ais_run_mix(&a, sap, map, st), what);
     } else {
-        chk(fabhip_ais_phase_smc(&a, sap, FABHIP_AIS_INIT, 1, 0, nullptr, st), "ais_run (chain initialisation)");
+        chk(fabhip_ais_phase_mix(&a, sap, map, FABHIP_AIS_INIT, 1, 0, nullptr, st),
+            map ? "ais_run_mix (chain initialisation)" : "ais_run (chain initialisation)");
         noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
         noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
         a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
         smc_outputs();
-        chk(fabhip_ais_phase_smc(&a, sap, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
-            "ais_run (transitions)");
+        chk(fabhip_ais_phase_mix(&a, sap, map, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
+            map ? "ais_run_mix (transitions)" : "ais_run (transitions)");
     }
     return {x, lq, lp, gq, gp, log_w, o.n_valid, o.stats, o.base_x, o.base_lw};
 }
@@ -1039,6 +1070,49 @@ std::vector<Tensor> ais_run_smc(
     return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
             std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
             e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
+}
+
+// ais_run_smc with the defensive mixture as base distribution (fabhip_ais_run_mix): the fourteen outputs of ais_run_smc.
+// `enabled` = false: the call without the mixture through the same entry points (launch for launch the plain call).
+std::vector<Tensor> ais_run_mix(
+    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
+    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
+    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
+    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
+    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, const Tensor& loc,
+    const Tensor& log_scale, const Tensor& logit, const optional<Tensor>& sel, bool enabled) {
+    MixOp mix;
+    mix.enabled = enabled; mix.loc = loc; mix.log_scale = log_scale; mix.logit = logit; mix.sel = sel;
+    SmcOp smc;
+    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.mix = &mix;
+    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
+    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
+    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
+            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
+            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
+}
+
+// The mixture's density (and d/dx with with_grad) at x [B, dim]: one launch (fabhip_defensive_log_prob).
+std::tuple<Tensor, Tensor> defensive_log_prob(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, const Tensor& loc,
+                                              const Tensor& log_scale, const Tensor& logit, const Tensor& x, bool with_grad,
+                                              int64_t precision) {
+    c10::DeviceGuard g(x.device());
+    TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
+    const fabhip_flow f = make_flow(packed, dim, n_layers, width, precision);
+    need_n(packed, packed.numel(), x, "packed flow image");
+    MixOp mix;
+    mix.loc = loc; mix.log_scale = log_scale; mix.logit = logit;
+    const fabhip_defensive_args ma = make_mix(mix, dim, x);
+    const int64_t B = x.size(0);
+    Tensor lq = fempty({B}, x), gx = with_grad ? fempty({B, dim}, x) : fempty({0}, x);
+    chk(fabhip_defensive_log_prob(&f, &ma, fp(x, "x"), lq.data_ptr<float>(), with_grad ? gx.data_ptr<float>() : nullptr, B,
+                                  nullptr, stream_of(x)),
+        "defensive_log_prob");
+    return {lq, gx};
 }
 
 // The same call in pieces (fabhip_ais_phase): the state tensors are the caller's, in/out across the phases of one AIS
@@ -1527,6 +1601,14 @@ TORCH_LIBRARY(fabhip, m) {
           "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
           "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
           "Tensor? noise_r, bool want_trace) -> Tensor[]");
+    m.def("ais_run_mix(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
+          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
+          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
+          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
+          "Tensor? noise_r, bool want_trace, Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor? sel, "
+          "bool enabled=True) -> Tensor[]");
+    m.def("defensive_log_prob(" FLW ", Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor x, bool with_grad, "
+          "int precision=0) -> (Tensor, Tensor)");
     m.def("ais_phase_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
           "int j_end, Tensor? eps0, Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, "
           "Tensor? mass, int n_inner, int L, float max_grad, float target_p_accept, bool tune, Tensor(c!) x, "
@@ -1621,6 +1703,8 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("ais_phase", Plain<ais_phase_core>::op);
     m.impl("ais_run_smc", ais_run_smc);
     m.impl("ais_phase_smc", ais_phase_smc);
+    m.impl("ais_run_mix", ais_run_mix);
+    m.impl("defensive_log_prob", defensive_log_prob);
     m.impl("smc_decide", smc_decide);
     m.impl("smc_shard_pack", smc_shard_pack);
     m.impl("smc_shard_resample", smc_shard_resample);

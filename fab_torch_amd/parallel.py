@@ -114,6 +114,16 @@ def refuse_resampling(who: str, threshold):
                           "ranks when it is built with resample_across_ranks=True)")
 
 
+def refuse_mixture(who: str, sampler):
+    """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_run_mix has no `partials` form and
+    the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
+    from .defensive import DefensiveMixtureDistribution
+    if isinstance(getattr(sampler, "base_distribution", None), DefensiveMixtureDistribution):
+        from ._ops import FabhipError
+        raise FabhipError(f"{who}: a DefensiveMixtureDistribution base distribution is not available for sharded chains; "
+                          "run the mixture on one device (AnnealedImportanceSampler), or shard the plain flow")
+
+
 class ShardedAIS:
     """`sample_and_log_weights(total_batch)` over all ranks.
 
@@ -132,6 +142,7 @@ class ShardedAIS:
         rank = dist.get_rank(self.group) if dist.is_initialized() else 0
         sizes = shard_sizes(total_batch, world)
         refuse_resampling("ShardedAIS", getattr(getattr(self.local_sampler, "__self__", None), "resample_threshold", None))
+        refuse_mixture("ShardedAIS", getattr(self.local_sampler, "__self__", None))
         x, log_w, log_q = self.local_sampler(sizes[rank])
         if self.sync_step_size and self.step_state is not None and world > 1:
             # ONE tiny all-reduce for all step-size tensors (epsilons [M, n_outer] + common_epsilon [1]: latency-bound)
@@ -154,6 +165,7 @@ class HipShardBackend:
     def __init__(self, ais):
         from . import _ops
         from .transition_operators import HamiltonianMonteCarlo
+        refuse_mixture("ShardedAnnealedImportanceSampler", ais)
         self.ais, self.ops, self._ops_mod = ais, _ops.load(), _ops
         self.op = ais.transition_operator
         self.hmc = isinstance(self.op, HamiltonianMonteCarlo)

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 220
+#define FABHIP_ABI_VERSION 221
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -635,6 +635,34 @@ size_t fabhip_ais_smc_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner);
 int fabhip_ais_run_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, fabhip_stream_t stream);
 int fabhip_ais_phase_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin,
                          int32_t j_end, float* partials, fabhip_stream_t stream);
+
+/* Defensive-mixture base distribution (fab/trainable_distributions/defensive_mixture.py; definition: tests/defensive_spec.py):
+ *   log q(x) = logsumexp(log q_flow(x) + logsigmoid(l), log N(x; loc, exp(log_scale)) + logsigmoid(-l)),   l = logit[0],
+ * which bounds the AIS target p^2 / q wherever the Gaussian has mass - also where the flow's float32 density underflows.
+ * Gradient in closed form: r_f d log q_flow/dx + (1 - r_f) (-(x - loc) exp(-2 log_scale)), r_f = exp(a - log q) the flow's
+ * responsibility (exactly 0, and the flow's gradient ignored, where log q_flow = -inf).  Chain initialisation: row i keeps the
+ * flow's sample of eps0[i] iff sel[i] < sigmoid(l), else x = loc + exp(log_scale) eps0[i]; log q0 is the mixture density at x.
+ * The kernels read the three parameter tensors directly (device; no packed copy, no host read).  The mode runs on the 16-chain
+ * tiles at every batch size, fp32 only (FABHIP_PRECISION_FAST / the process-wide fast mode: FABHIP_ENOTSUP), not with
+ * `partials` (sharded chains: FABHIP_ENOTSUP).  `enabled` == 0 (or a NULL fabhip_defensive_args): the call without the mixture,
+ * launch for launch. */
+typedef struct {
+    int32_t enabled;
+    const float* loc;         /* device [dim]                                                                       */
+    const float* log_scale;   /* device [dim]                                                                       */
+    const float* logit;       /* device [1]: P(flow branch) = sigmoid(logit)                                        */
+    const float* sel;         /* device [B] uniforms in [0, 1): the branch draws; read by FABHIP_AIS_INIT only      */
+} fabhip_defensive_args;
+/* fabhip_ais_run_smc / fabhip_ais_phase_smc with the mixture as base distribution (smc may be NULL; the two modes compose: only
+ * the point and log_w move in a resampling step).  Workspace: as for the same call without the mixture. */
+int fabhip_ais_run_mix(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                       fabhip_stream_t stream);
+int fabhip_ais_phase_mix(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                         int32_t phases, int32_t j_begin, int32_t j_end, float* partials, fabhip_stream_t stream);
+/* The mixture's density alone: log_q [B] and, with grad_x != NULL, d log q / dx [B][dim] at x [B][dim] - one launch, for
+ * operators stepped from the host.  `mix->sel` is not read.  `workspace`: reserved, may be NULL. */
+int fabhip_defensive_log_prob(const fabhip_flow* flow, const fabhip_defensive_args* mix, const float* x, float* log_q,
+                              float* grad_x, int64_t B, void* workspace, fabhip_stream_t stream);
 
 /* The decision alone, for samplers that step their transitions themselves (the generic plug-in path): ancestors [B] (identity
  * where nothing is resampled and beyond *n_ptr rows), resampled [1], log_w_common [1] (the value every log_w[:n0] takes when
