@@ -793,7 +793,8 @@ int fabhip_multinomial_torch(const float* probs, int64_t n, const double* u, int
  *   multinomial: idx_k = first j with C_j > floor(u_k * C_total)                (decoupled look-back scan + search)
  *   systematic : idx_k = first j with C_j > floor((k + u0) * (C_total / n_samples))
  *                fused: wave-tile sums -> tile prefix -> every tile emits the strata that fall inside its CDF range;
- *                the CDF never touches HBM (12n + 8 n_samples bytes of traffic).                              */
+ *                the CDF never touches HBM (12n + 8 n_samples bytes of traffic).
+ * Non-finite rows weigh 0; C_total == 0 (every weight dead): every index of both samplers is n - 1. */
 size_t fabhip_resample_workspace_bytes(int64_t n);
 /* The fixed-point inclusive CDF C[0..n) (uint64) of log-weights, built in the workspace by ONE decoupled-look-back scan
  * pass (4n bytes read, 8n written) after a max pass (4n read); *cdf_out (host pointer-to-device-pointer, may be
