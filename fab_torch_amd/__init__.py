@@ -17,8 +17,8 @@ from .buffer import PrioritisedReplayBuffer, sample_without_replacement
 from .train import PrioritisedBufferTrainer, Trainer
 from .optim import FlatAdam
 from .spline_flow import CircularCoupledRQSFlow, make_wrapped_normflow_spline
-from .resample import (resample, multinomial_indices, systematic_indices, multinomial_stream_indices, multinomial_torch_compat,
-                       gather_rows)
+from .resample import (resample, multinomial_indices, systematic_indices, multinomial_stream_indices, stratified_indices,
+                       multinomial_torch_compat, gather_rows)
 
 
 
@@ -45,7 +45,7 @@ __all__ = [
     "HamiltonianMonteCarlo", "Metropolis", "create_point", "grad_and_value", "get_intermediate_log_prob",
     "get_grad_intermediate_log_prob", "AnnealedImportanceSampler", "LoggingInfo", "NoValidPoints",
     "effective_sample_size", "ess_and_log_z", "resample", "multinomial_indices", "systematic_indices",
-    "multinomial_stream_indices", "multinomial_torch_compat", "gather_rows", "FABModel", "PrioritisedReplayBuffer",
+    "multinomial_stream_indices", "stratified_indices", "multinomial_torch_compat", "gather_rows", "FABModel", "PrioritisedReplayBuffer",
     "sample_without_replacement", "PrioritisedBufferTrainer", "Trainer", "FlatAdam", "CircularCoupledRQSFlow", "make_wrapped_normflow_spline", "fast_mode",
     "DefensiveMixtureDistribution",
 ]

@@ -86,7 +86,8 @@ _lock = threading.Lock()
 
 class SmcArgs(C.Structure):       # fabhip_smc_args
     _fields_ = [("enabled", C.c_int32), ("only_resample", C.c_int32), ("tau", C.c_double), ("u", C.c_void_p),
-                ("resampled", C.c_void_p), ("ess", C.c_void_p), ("ancestors", C.c_void_p), ("log_w_pre", C.c_void_p)]
+                ("resampled", C.c_void_p), ("ess", C.c_void_p), ("ancestors", C.c_void_p), ("log_w_pre", C.c_void_p),
+                ("method", C.c_int32)]           # FABHIP_SMC_SYSTEMATIC = 0, FABHIP_SMC_STRATIFIED = 1
 
 
 class DefensiveArgs(C.Structure):       # fabhip_defensive_args
@@ -121,8 +122,9 @@ SYMBOLS = [
     "fabhip_train_step_plan", "fabhip_resample_stream_workspace_bytes", "fabhip_resample_multinomial_stream",
     "fabhip_smc_shard_workspace_bytes", "fabhip_smc_shard_pack", "fabhip_smc_shard_resample",
     "fabhip_ais_run_mix", "fabhip_ais_phase_mix", "fabhip_defensive_log_prob",
+    "fabhip_resample_stratified_workspace_bytes", "fabhip_resample_stratified",
 ]
-ABI_VERSION = 221          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 222          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -159,7 +161,7 @@ def _declare(lib):
     lib.fabhip_defensive_log_prob.argtypes = [C.POINTER(Flow), C.POINTER(DefensiveArgs), vp, vp, vp, i64, vp, vp]
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]
-    lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
     lib.fabhip_smc_shard_workspace_bytes.restype = sz
     lib.fabhip_smc_shard_workspace_bytes.argtypes = [i32, i64]
     lib.fabhip_smc_shard_pack.argtypes = [C.POINTER(Point), vp, vp, i64, i32, vp, vp]
@@ -186,6 +188,9 @@ def _declare(lib):
     lib.fabhip_resample_stream_workspace_bytes.restype = sz
     lib.fabhip_resample_stream_workspace_bytes.argtypes = [i64, i64]
     lib.fabhip_resample_multinomial_stream.argtypes = [vp, i64, C.c_uint64, i64, i32, vp, vp, sz, vp]
+    lib.fabhip_resample_stratified_workspace_bytes.restype = sz
+    lib.fabhip_resample_stratified_workspace_bytes.argtypes = [i64, i64]
+    lib.fabhip_resample_stratified.argtypes = [vp, i64, C.c_uint64, i64, i32, vp, vp, sz, vp]
     lib.fabhip_gather_rows.argtypes = [vp, vp, vp, i64, i64, vp]
     lib.fabhip_debug_timeline.argtypes = [vp, i32]
     lib.fabhip_flow_grad_floats.restype = i64

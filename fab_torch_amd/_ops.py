@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 221          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 222          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM = 1, 2
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -249,8 +249,12 @@ def _register_fakes():
     def _(log_w, seed, n_samples, order):
         return log_w.new_empty((n_samples,), dtype=torch.int64)
 
+    @rf("fabhip::resample_stratified")
+    def _(log_w, seed, n_samples, order):
+        return log_w.new_empty((n_samples,), dtype=torch.int64)
+
     @rf("fabhip::smc_decide")
-    def _(log_w, tau, u):
+    def _(log_w, tau, u, method=0):
         return (log_w.new_empty((log_w.shape[0],), dtype=torch.int64), log_w.new_empty((1,), dtype=torch.int32),
                 log_w.new_empty((1,)), log_w.new_empty((1,)))
 

@@ -63,6 +63,15 @@ def operator_slots(op) -> Tuple[int, OperatorSlots]:
     raise _ops.FabhipError("transition_operator must be a fab_torch_amd HamiltonianMonteCarlo / Metropolis")
 
 
+RESAMPLE_METHODS = {"systematic": 0, "stratified": 1}      # FABHIP_SMC_SYSTEMATIC / FABHIP_SMC_STRATIFIED
+
+
+def check_resample_method(method) -> str:
+    if not isinstance(method, str) or method not in RESAMPLE_METHODS:
+        raise _ops.FabhipError(f"resample_method must be one of {sorted(RESAMPLE_METHODS)} (got {method!r})")
+    return method
+
+
 def _check_threshold(tau):
     if tau is None:
         return None
@@ -75,14 +84,21 @@ class AnnealedImportanceSampler:
     """`resample_threshold` (SMC mode, default None = plain AIS): before every transition the ESS of the current log-weights is
     computed on the device; below the threshold the chains are resampled in proportion to their weights (systematic, on the
     fixed-point CDF of `resample_systematic`) and continue with equal weights whose logsumexp is unchanged, so `log_Z`, the FAB
-    loss and the buffer see an ordinary `(point, log_w)`.  > 1: before every transition; 0: never (the decision still runs)."""
+    loss and the buffer see an ordinary `(point, log_w)`.  > 1: before every transition; 0: never (the decision still runs).
+    `resample_method` ("systematic", the default, or "stratified") chooses the ancestors of a resampling step: "stratified" draws
+    one offset per stratum (a hash of the transition's uniform and the stratum number; include/fabhip.h:
+    fabhip_resample_stratified) instead of one for all of them - unbiased like the systematic scheme, but with a variance that is
+    never above multinomial resampling's whatever the order of the chains.  The decision, `noise_r` and its draws are the same
+    for both; without `resample_threshold` the setting is inert."""
 
     def __init__(self, base_distribution, target_log_prob, transition_operator: TransitionOperator,
                  p_target: bool, alpha: Optional[float] = None, n_intermediate_distributions: int = 1,
-                 distribution_spacing_type: str = "linear", resample_threshold: Optional[float] = None):
+                 distribution_spacing_type: str = "linear", resample_threshold: Optional[float] = None,
+                 resample_method: str = "systematic"):
         if not p_target:
             assert alpha is not None, "Must specify alpha if AIS target is not p."
         self.resample_threshold = resample_threshold
+        self.resample_method = resample_method
         self.last_smc = None              # (resampled [M], ess [M], ancestors [M, B], log_w_pre [M, B]) of the last fused call
         self.base_distribution = base_distribution
         self.target_log_prob = target_log_prob
@@ -102,6 +118,14 @@ class AnnealedImportanceSampler:
     @resample_threshold.setter
     def resample_threshold(self, tau):
         self.__dict__["_resample_threshold"] = _check_threshold(tau)
+
+    @property
+    def resample_method(self) -> str:
+        return self.__dict__.get("_resample_method", "systematic")   # (a sampler restored from a state that predates the setting)
+
+    @resample_method.setter
+    def resample_method(self, method):
+        self.__dict__["_resample_method"] = check_resample_method(method)
 
     def _refuse_resampling(self, what: str):
         if self.resample_threshold is not None:
@@ -230,13 +254,13 @@ class AnnealedImportanceSampler:
             # defensive mixture: the same call through ais_run_mix (16-chain tiles, fp32; composes with the SMC mode)
             mix._refuse_fast()
             out = ops.ais_run_mix(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), tau,
-                                  noise_r, bool(trace), *mix.mix_args(), sel, True)
+                                  noise_r, bool(trace), *mix.mix_args(), sel, True, RESAMPLE_METHODS[self.resample_method])
             if tau is None:
                 out = out[:10]
         else:
             # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
             call = ops.ais_run if tau is None else ops.ais_run_smc
-            smc = () if tau is None else (tau, noise_r, bool(trace))
+            smc = () if tau is None else (tau, noise_r, bool(trace), RESAMPLE_METHODS[self.resample_method])
             out = call(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), *smc)
         if tau is not None:
             self.last_smc = tuple(out[10:14])
@@ -398,7 +422,7 @@ class AnnealedImportanceSampler:
         existing row gather; no host synchronisation (the gather runs with identity ancestors when nothing is resampled)."""
         ops = _ops.load()
         log_w = log_w.contiguous()
-        anc, flag, ess, common = ops.smc_decide(log_w, float(self.resample_threshold), u)
+        anc, flag, ess, common = ops.smc_decide(log_w, float(self.resample_threshold), u, RESAMPLE_METHODS[self.resample_method])
         g = lambda t: None if t is None else ops.gather_rows(t.detach().contiguous().float().view(t.shape[0], -1),      # noqa: E731
                                                              anc).view(t.shape)
         point = Point(g(point.x), g(point.log_q), g(point.log_p), g(point.grad_log_q), g(point.grad_log_p))

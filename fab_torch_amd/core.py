@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .ais import AnnealedImportanceSampler
+from .ais import AnnealedImportanceSampler, check_resample_method
 from .numerical import effective_sample_size
 from .point import Point
 from .transition_operators import TransitionOperator
@@ -29,9 +29,11 @@ SUPPORTED_LOSSES = [None, "fab_alpha_div", "forward_kl", "flow_reverse_kl", "flo
 class FABModel:
     def __init__(self, flow, target_distribution, n_intermediate_distributions: int, alpha: float = 2.,
                  transition_operator: Optional[TransitionOperator] = None, ais_distribution_spacing: str = "linear",
-                 loss_type: Optional[str] = None, use_ais: bool = True, ais_resample_threshold: Optional[float] = None):
+                 loss_type: Optional[str] = None, use_ais: bool = True, ais_resample_threshold: Optional[float] = None,
+                 ais_resample_method: str = "systematic"):
         assert loss_type in SUPPORTED_LOSSES
         self.ais_resample_threshold = ais_resample_threshold       # SMC mode of the sampler (ais.py), None: plain AIS
+        self.ais_resample_method = check_resample_method(ais_resample_method)   # "systematic" / "stratified" ancestors of that mode
         if loss_type in EXPERIMENTAL_LOSSES:               # same refusal as the reference (core.py:50-51)
             raise Exception("Running using experiment loss not used within the main FAB paper.")
         if loss_type in ALPHA_DIV_TARGET_LOSSES:
@@ -55,7 +57,8 @@ class FABModel:
             transition_operator=self.transition_operator, p_target=False, alpha=self.alpha,
             n_intermediate_distributions=self.n_intermediate_distributions,
             distribution_spacing_type=self.ais_distribution_spacing,
-            resample_threshold=getattr(self, "ais_resample_threshold", None))
+            resample_threshold=getattr(self, "ais_resample_threshold", None),
+            resample_method=getattr(self, "ais_resample_method", "systematic"))
 
     def parameters(self):
         return self.flow.parameters()

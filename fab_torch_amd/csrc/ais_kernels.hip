@@ -2048,6 +2048,7 @@ int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, c
     if (mx.on && (partials || resolve_fast(a->flow.precision))) return FABHIP_ENOTSUP;    // (sharded chains, bf16 fast mode)
     if (mx.on && do_init && !mix->sel) return FABHIP_EINVAL;                              // (like eps0: read by INIT only)
     if (smc_on && partials) return FABHIP_ENOTSUP;
+    if (smc_on && smc->method != FABHIP_SMC_SYSTEMATIC && smc->method != FABHIP_SMC_STRATIFIED) return FABHIP_EINVAL;
     if (smc_on && j_begin <= j_end && !smc->u) return FABHIP_EINVAL;                  // (like the noise: read by the transitions only)
     if (a->workspace_bytes < (smc_on ? fabhip_ais_smc_workspace_bytes(a->B, a->flow.dim, a->n_inner)
                                      : fabhip_ais_workspace_bytes(a->B, a->flow.dim, a->n_inner))) return FABHIP_ENOSPC;
@@ -2142,6 +2143,7 @@ int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, c
             k.ess_out = smc->ess ? smc->ess + (j - 1) : nullptr;
             k.anc_out = smc->ancestors ? smc->ancestors + (size_t)(j - 1) * B : nullptr;
             k.lw_pre_out = smc->log_w_pre ? smc->log_w_pre + (size_t)(j - 1) * B : nullptr;
+            k.method = smc->method;
             FAB_TRY(smc_decide(k, st));
             SmcGatherK g{make_point_dev(a->point), a->log_w, tmp, smc_anc, smc_flag, smc_lw, a->n_valid, B, D};
             const int grid = (int)(B < 4096 ? B : 4096);

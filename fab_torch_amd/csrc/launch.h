@@ -99,8 +99,8 @@ int tail_small(const TailArgs& a, int* dest, hipStream_t st);
 
 // The decision of the SMC mode (include/fabhip.h: fabhip_smc_args; reduce_resample.hip: k_smc_decide), one workgroup: fixed-point
 // weights W of log_w[:n0] (the resampler's own exp_spec / fixed_weight), their integer CDF, ESS = (sum W)^2 / (n0 sum W^2) from
-// exact integer sums, the device flag `ESS < tau`, the common log-weight after resampling and the systematic ancestors of the
-// first n0 rows (identity where the flag is off, and for the rows beyond n0).
+// exact integer sums, the device flag `ESS < tau`, the common log-weight after resampling and the systematic (or stratified:
+// `method`) ancestors of the first n0 rows (identity where the flag is off, and for the rows beyond n0).
 struct SmcK {
     const float* log_w;                // [B]
     const int* n_ptr;                  // rows in use (device; null: B)
@@ -115,6 +115,7 @@ struct SmcK {
     float* ess_out;                    // optional [1]
     int* anc_out;                      // optional [B] (a second copy: the caller's record)
     float* lw_pre_out;                 // optional [B]: log_w as the decision saw it
+    int method = 0;                    // FABHIP_SMC_SYSTEMATIC / FABHIP_SMC_STRATIFIED (the seed of the latter: the 64 bits of *u)
 };
 int smc_decide(const SmcK& a, hipStream_t st);
 

@@ -1047,14 +1047,58 @@ __device__ __forceinline__ int stratum_rel_small(const Strata& m, long long Bw, 
     return C_abs >= m.total ? ns_rel : k;
 }
 
-__global__ __launch_bounds__(64 * EM_NW) void k_emit_systematic(const float* __restrict__ lw, long n,
-                                                                const float* __restrict__ max_val,
-                                                                const unsigned long long* __restrict__ wave_sum,
-                                                                const unsigned long long* __restrict__ block_excl,
-                                                                const unsigned long long* __restrict__ strata_ptr,
-                                                                long ns, long long* __restrict__ idx,
-                                                                unsigned long long* __restrict__ giant_count,
-                                                                long long* __restrict__ giant_desc, long giant_cap) {
+// Stratified resampling (include/fabhip.h: fabhip_resample_stratified; tests/resample_stratified_spec.py restates it): one
+// hashed offset per stratum, t_k = (k S + U_k) >> F with U_k = hi64(ms_hash(seed, k) * S) in [0, S - 1].  The thresholds are
+// still sorted, one per stratum, so the inverse stays a closed form: with B = C << F and q = min(floor(B / S), ns)
+//     K(C) = #{k : t_k < C} = q + [q < ns and U_q < B - q S]
+// (strata below q end at or below B, strata above q start above it; only stratum q needs its hash).  Both functions below take
+// an ESTIMATE of q, make it exact with one integer step on the remainder R = B - q S, and let the hash of the exact q decide.
+__device__ __forceinline__ unsigned long long ms_hash(unsigned long long seed, unsigned long long i);
+
+// K(c0 + d) - Kref as int32: float64 estimate of floor(((c0 + d) << F) / S) (B < 2^62, q <= ns + 1 < 2^31: the three rounded
+// operations lose < 2^-20 of a stratum), B0d = (double)(c0 << F) supplied by the caller.
+__device__ __forceinline__ int stratified_rel(const Strata& m, unsigned long long seed, unsigned long long c0,
+                                              unsigned long long d, double B0d, double pow2F, double invS, long Kref, long ns) {
+    const unsigned long long B = (c0 + d) << m.F;
+    long long q = (long long)(((double)d * pow2F + B0d) * invS);
+    long long R = (long long)(B - (unsigned long long)q * m.S);              // |R| < 2 S < 2^63
+    if (R < 0) { --q; R += (long long)m.S; }
+    else if (R >= (long long)m.S) { ++q; R -= (long long)m.S; }
+    if (q >= ns) return (int)(ns - Kref);
+    const unsigned long long Uq = __umul64hi(ms_hash(seed, (unsigned long long)q), m.S);
+    return (int)(q + (Uq < (unsigned long long)R ? 1 : 0) - Kref);
+}
+
+// The same for the items of ONE wave whose strata span T < 2^20, relative to the stratum q0 = floor((c_start << F) / S) that
+// holds the wave's start: X = Bw + (d << F) with the wave constant Bw = (c_start << F) - q0 S in [0, S), so the quotient
+// floor(X / S) <= T + 1 is small and an fp32 estimate is off by less than one stratum (as in stratum_rel_small).  koff = K0 - q0
+// (0 or 1) turns the count into one relative to the wave's first stratum K0.  Same value as stratified_rel(..., Kref = K0).
+__device__ __forceinline__ int stratified_rel_small(const Strata& m, unsigned long long seed, unsigned long long Bw, float invS_f,
+                                                    unsigned long long q0, unsigned long long d, int koff, long ns, int ns_rel) {
+    const unsigned long long X = Bw + (d << m.F);
+    const float xf = (float)(unsigned)(X >> 32) * 4294967296.0f + (float)(unsigned)X;
+    int k = (int)(xf * invS_f);
+    long long R = (long long)(X - (unsigned long long)(unsigned)k * m.S);    // X - k S, exact
+    const bool lo = R < 0, hi = R >= (long long)m.S;
+    k += hi ? 1 : (lo ? -1 : 0);
+    R += lo ? (long long)m.S : (hi ? -(long long)m.S : 0ll);
+    const unsigned long long q = q0 + (unsigned long long)(unsigned)k;
+    const unsigned long long Uq = __umul64hi(ms_hash(seed, q), m.S);
+    const int r = k + (Uq < (unsigned long long)R ? 1 : 0) - koff;
+    return q >= (unsigned long long)ns ? ns_rel : r;
+}
+
+// The emitter of the systematic (STRAT = false) and of the stratified resampler (STRAT = true; `seed` is read by that one only):
+// the two differ in the stratum ranges ke[] alone.
+template <bool STRAT>
+__device__ __forceinline__ void emit_runs(const float* __restrict__ lw, long n,
+                                          const float* __restrict__ max_val,
+                                          const unsigned long long* __restrict__ wave_sum,
+                                          const unsigned long long* __restrict__ block_excl,
+                                          const unsigned long long* __restrict__ strata_ptr,
+                                          long ns, long long* __restrict__ idx,
+                                          unsigned long long* __restrict__ giant_count,
+                                          long long* __restrict__ giant_desc, long giant_cap, unsigned long long seed) {
     __shared__ __attribute__((aligned(16))) unsigned char em_lds[EM_NW * EM_WAVE_LDS];
     typedef long long i64x2 __attribute__((ext_vector_type(2)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1107,12 +1151,29 @@ __global__ __launch_bounds__(64 * EM_NW) void k_emit_systematic(const float* __r
     // ---- stratum ranges relative to K0 = K(c_start): item j owns [ke[j-1], ke[j]) (ke[-1] = previous lane's ke[15]) ----
     const double pow2F = (double)(1ull << m.F), invS = 1.0 / (double)m.S;
     const unsigned long long B0 = c_start << m.F;
-    const double num0 = B0 >= m.U ? (double)(B0 - m.U) : -(double)(m.U - B0);
-    const long K0 = (long)stratum_rel(m, c_start, 0ull, num0, pow2F, invS, 0, ns) ;   // wave-uniform (Kref = 0: < 2^31)
-    const int T = stratum_rel(m, c_start, wtot, num0, pow2F, invS, K0, ns);            // strata owned by this wave (uniform)
+    const double num0 = STRAT ? (double)B0 : (B0 >= m.U ? (double)(B0 - m.U) : -(double)(m.U - B0));
+    const long K0 = STRAT ? (long)stratified_rel(m, seed, c_start, 0ull, num0, pow2F, invS, 0, ns)
+                          : (long)stratum_rel(m, c_start, 0ull, num0, pow2F, invS, 0, ns);   // wave-uniform (Kref = 0: < 2^31)
+    const int T = STRAT ? stratified_rel(m, seed, c_start, wtot, num0, pow2F, invS, K0, ns)
+                        : stratum_rel(m, c_start, wtot, num0, pow2F, invS, K0, ns);          // strata owned by this wave (uniform)
     if (T <= 0) return;
     int ke[16];
-    if (T < (1 << 20)) {                                   // wave-uniform: the usual case
+    if constexpr (STRAT) {
+        if (T < (1 << 20)) {                               // wave-uniform: the usual case
+            const unsigned long long q0 = B0 / m.S;        // the stratum that holds c_start: K0 - q0 is 0 or 1 (T > 0: q0 < ns)
+            const unsigned long long Bw = B0 - q0 * m.S;
+            const float invS_f = 1.0f / (float)m.S;
+            const int koff = (int)(K0 - (long)q0), ns_rel = (int)(ns - K0);
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                ke[j] = stratified_rel_small(m, seed, Bw, invS_f, q0, lane_off + run[j], koff, ns, ns_rel);
+        } else {                                           // giant runs: float64 estimate per item
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                ke[j] = (j > 0 && run[j] == run[j - 1]) ? ke[j - 1]
+                                                        : stratified_rel(m, seed, c_start, lane_off + run[j], num0, pow2F, invS, K0, ns);
+        }
+    } else if (T < (1 << 20)) {                            // wave-uniform: the usual case
         const long long Bw = (long long)(B0 - m.U - (unsigned long long)K0 * m.S);
         const float invS_f = 1.0f / (float)m.S;
         const int ns_rel = (int)(ns - K0);
@@ -1137,7 +1198,10 @@ __global__ __launch_bounds__(64 * EM_NW) void k_emit_systematic(const float* __r
         for (int j = 0; j < 16; ++j) {
             if (ke[j] - sg >= EM_GIANT) {
                 const unsigned long long slot = atomicAdd(giant_count, 1ull);
-                if ((long)slot < giant_cap) {              // (list full: the run stays with this wave)
+                // (list full: the run stays with this wave.  Reached through k_emit_systematic only: fabhip_resample_stratified
+                //  carves its list for ns / EM_GIANT + 1 runs, more than can exist, so for STRAT this is a bound on the store
+                //  below that never binds - kept as that, tested through the systematic cases list_full / no_list)
+                if ((long)slot < giant_cap) {
                     long id = item0 + 16 * lane + j;
                     giant_desc[3 * slot] = K0 + sg; giant_desc[3 * slot + 1] = K0 + ke[j];
                     giant_desc[3 * slot + 2] = id < n ? id : n - 1;
@@ -1220,6 +1284,29 @@ __global__ __launch_bounds__(64 * EM_NW) void k_emit_systematic(const float* __r
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+__global__ __launch_bounds__(64 * EM_NW) void k_emit_systematic(const float* __restrict__ lw, long n,
+                                                                const float* __restrict__ max_val,
+                                                                const unsigned long long* __restrict__ wave_sum,
+                                                                const unsigned long long* __restrict__ block_excl,
+                                                                const unsigned long long* __restrict__ strata_ptr,
+                                                                long ns, long long* __restrict__ idx,
+                                                                unsigned long long* __restrict__ giant_count,
+                                                                long long* __restrict__ giant_desc, long giant_cap) {
+    emit_runs<false>(lw, n, max_val, wave_sum, block_excl, strata_ptr, ns, idx, giant_count, giant_desc, giant_cap, 0ull);
+}
+
+// (strata_ptr: k_emit_prefix with u0 = 0, i.e. {total, S, 0, F})
+__global__ __launch_bounds__(64 * EM_NW) void k_emit_stratified(const float* __restrict__ lw, long n,
+                                                                const float* __restrict__ max_val,
+                                                                const unsigned long long* __restrict__ wave_sum,
+                                                                const unsigned long long* __restrict__ block_excl,
+                                                                const unsigned long long* __restrict__ strata_ptr,
+                                                                long ns, unsigned long long seed, long long* __restrict__ idx,
+                                                                unsigned long long* __restrict__ giant_count,
+                                                                long long* __restrict__ giant_desc, long giant_cap) {
+    emit_runs<true>(lw, n, max_val, wave_sum, block_excl, strata_ptr, ns, idx, giant_count, giant_desc, giant_cap, seed);
 }
 
 // constant fill of the published giant runs: workgroup b takes 16384-entry chunks (run r, chunk c) round-robin
@@ -1779,7 +1866,9 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_decide(SmcK a) {
         double u0 = *a.u;
         if (!(u0 >= 0.0 && u0 < 1.0)) u0 = 0.0;
         const Strata m = make_strata(total, u0, n0 > 0 ? n0 : 1);
-        sh_S = m.S; sh_U = m.U; sh_F = m.F; sh_fire = fire;
+        // (stratified: the offset word carries the seed - the 64 bits of u - and every stratum hashes its own offset from it)
+        sh_S = m.S; sh_U = a.method == FABHIP_SMC_STRATIFIED ? (unsigned long long)__double_as_longlong(u0) : m.U;
+        sh_F = m.F; sh_fire = fire;
         *a.flag = fire;
         // log of the mean weight: log_Z = logsumexp(log_w) - log(B) of the tail kernel is unchanged by the resampling
         *a.lw_common = fire ? (float)((double)mx + log(S1 * 1.4551915228366852e-11 / (double)n0)) : 0.f;
@@ -1787,14 +1876,17 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_decide(SmcK a) {
         if (a.ess_out) *a.ess_out = (float)ess;
     }
     __syncthreads();
-    // 4. ancestors: first j with C[j] > t_k, t_k = (k S + U) >> F (oracle/numerical.py: systematic_fixed)
+    // 4. ancestors: first j with C[j] > t_k, t_k = (k S + U) >> F (oracle/numerical.py: systematic_fixed); stratified:
+    //    U = U_k = hi64(ms_hash(seed, k) * S) (tests/resample_stratified_spec.py)
     const bool fire = sh_fire != 0;
+    const bool strat = a.method == FABHIP_SMC_STRATIFIED;
     const unsigned long long S = sh_S, U = sh_U;
     const int F = sh_F;
     for (long k = tid; k < a.B; k += SMC_THREADS) {
         long r = k;
         if (fire && k < n0) {
-            const unsigned long long t = ((unsigned long long)k * S + U) >> F;
+            const unsigned long long Uk = strat ? __umul64hi(ms_hash(U, (unsigned long long)k), S) : U;
+            const unsigned long long t = ((unsigned long long)k * S + Uk) >> F;
             long lo = 0, hi = n0;                       // first index with cdf > t
             while (lo < hi) {
                 const long mid = (lo + hi) >> 1;
@@ -1809,6 +1901,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_decide(SmcK a) {
 
 int smc_decide(const SmcK& a, hipStream_t st) {
     if (!a.log_w || !a.u || !a.cdf || !a.anc || !a.flag || !a.lw_common || a.B < 1 || a.B > 0x7fffffffL) return FABHIP_EINVAL;
+    if (a.method != FABHIP_SMC_SYSTEMATIC && a.method != FABHIP_SMC_STRATIFIED) return FABHIP_EINVAL;
     hipLaunchKernelGGL(k_smc_decide, dim3(1), dim3(SMC_THREADS), 0, st, a);
     return check_launch();
 }
@@ -2042,17 +2135,74 @@ int fabhip_resample_multinomial_stream(const float* log_w, int64_t n, uint64_t s
     return check_launch();
 }
 
+namespace {
+struct StratWs {          // workspace layout of the stratified resampler (all 256-byte aligned)
+    float* max_part; float* max_val;
+    unsigned long long *w_wave, *w_block, *w_excl, *w_strata;      // tile sums, block sums, prefix, {total, S, 0, F} + run counter
+    long long* giant_desc;                                         // [3 giant_cap]
+    long long* sorted;                                             // [n_samples] the sorted indices of order = shuffled
+    long nwt, nbk, giant_cap;
+    size_t bytes;
+};
+StratWs carve_strat_ws(void* workspace, long n, long ns) {
+    StratWs s;
+    s.nwt = (n + EM_WAVE_ITEMS - 1) / EM_WAVE_ITEMS; s.nbk = (n + EM_BLOCK - 1) / EM_BLOCK;
+    s.giant_cap = ns / EM_GIANT + 1;                               // at most ns / EM_GIANT runs can be that long
+    char* p = (char*)workspace;
+    auto take = [&](size_t b) { char* q = p; p += al256(b); return q; };
+    s.max_part = (float*)take(1024 * 4); s.max_val = (float*)take(4);
+    s.w_wave = (unsigned long long*)take((size_t)s.nbk * EM_NW * 8); s.w_block = (unsigned long long*)take((size_t)s.nbk * 8);
+    s.w_excl = (unsigned long long*)take((size_t)s.nbk * 8); s.w_strata = (unsigned long long*)take(64);
+    s.giant_desc = (long long*)take((size_t)s.giant_cap * 24);
+    s.sorted = (long long*)take((size_t)ns * 8);
+    s.bytes = (size_t)(p - (char*)workspace);
+    return s;
+}
+}  // namespace
+
+size_t fabhip_resample_stratified_workspace_bytes(int64_t n, int64_t n_samples) {
+    if (n < 1 || n_samples < 1 || n_samples > FABHIP_STRATIFIED_MAX_SAMPLES) return 0;
+    return carve_strat_ws(nullptr, (long)n, (long)n_samples).bytes;
+}
+
+int fabhip_resample_stratified(const float* log_w, int64_t n, uint64_t seed, int64_t n_samples, int32_t order, int64_t* idx,
+                               void* workspace, size_t workspace_bytes, fabhip_stream_t stream) {
+    if (!log_w || !idx || !workspace || n < 1 || n_samples < 1) return FABHIP_EINVAL;
+    if (order != FABHIP_ORDER_SORTED && order != FABHIP_ORDER_SHUFFLED) return FABHIP_EINVAL;
+    if (n_samples > FABHIP_STRATIFIED_MAX_SAMPLES) return FABHIP_EINVAL;
+    if (((size_t)workspace & 255) != 0) return FABHIP_EINVAL;
+    if (workspace_bytes < fabhip_resample_stratified_workspace_bytes(n, n_samples)) return FABHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const long ns = (long)n_samples;
+    const StratWs s = carve_strat_ws(workspace, (long)n, ns);
+    long long* out = order == FABHIP_ORDER_SHUFFLED ? s.sorted : (long long*)idx;
+    const int mb = grid_for(n, 256 * 16, 1024);
+    hipLaunchKernelGGL(k_max_partial, dim3(mb), dim3(256), 0, st, log_w, (long)n, s.max_part);
+    hipLaunchKernelGGL(k_max_final, dim3(1), dim3(256), 0, st, s.max_part, mb, s.max_val);
+    const dim3 grid((unsigned)s.nbk), block(64 * EM_NW);
+    hipLaunchKernelGGL(k_emit_wave_sums, grid, block, 0, st, log_w, (long)n, s.max_val, s.w_wave, s.w_block);
+    hipLaunchKernelGGL(k_emit_prefix, dim3(1), dim3(1024), 0, st, s.w_block, s.nbk, s.w_excl, 0.0, ns, s.w_strata, s.w_strata + 4);
+    hipLaunchKernelGGL(k_emit_stratified, grid, block, 0, st, log_w, (long)n, s.max_val, s.w_wave, s.w_excl, s.w_strata, ns,
+                       (unsigned long long)seed, out, s.w_strata + 4, s.giant_desc, s.giant_cap);
+    if (ns >= EM_GIANT)
+        hipLaunchKernelGGL(k_emit_fill_runs, dim3(256), dim3(256), 0, st, s.w_strata + 4, s.giant_desc, s.giant_cap, out);
+    if (order == FABHIP_ORDER_SHUFFLED)
+        hipLaunchKernelGGL(k_ms_shuffle, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, out, ns, (unsigned long long)seed,
+                           (long long*)idx);
+    return check_launch();
+}
+
 size_t fabhip_smc_workspace_bytes(int64_t B) { return al256((size_t)(B > 0 ? B : 0) * 8) + al256((size_t)(B > 0 ? B : 0) * 4) + 512; }
 
 int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
                       int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
-                      size_t workspace_bytes, fabhip_stream_t stream) {
+                      size_t workspace_bytes, int32_t method, fabhip_stream_t stream) {
     if (!log_w || !u || !ancestors || !resampled || !log_w_common || !workspace || B < 1) return FABHIP_EINVAL;
     if (workspace_bytes < fabhip_smc_workspace_bytes(B)) return FABHIP_ENOSPC;
     SmcK k;
     k.log_w = log_w; k.n_ptr = n_ptr; k.B = (long)B; k.tau = tau; k.u = u;
     k.cdf = (unsigned long long*)workspace; k.anc = ancestors; k.flag = resampled; k.lw_common = log_w_common;
-    k.resampled_out = nullptr; k.ess_out = ess; k.anc_out = nullptr; k.lw_pre_out = log_w_pre;
+    k.resampled_out = nullptr; k.ess_out = ess; k.anc_out = nullptr; k.lw_pre_out = log_w_pre; k.method = method;
     return smc_decide(k, (hipStream_t)stream);
 }
 

@@ -933,6 +933,7 @@ struct SmcOp {
     optional<double> tau;
     optional<Tensor> noise_r;
     bool want_trace = false;
+    int64_t method = 0;                                 // FABHIP_SMC_SYSTEMATIC / FABHIP_SMC_STRATIFIED
     Tensor resampled, ess, ancestors, log_w_pre, u;     // out (ais_run_smc)
     const MixOp* mix = nullptr;                         // ais_run_mix: the call goes through fabhip_ais_*_mix
 };
@@ -1006,7 +1007,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     a.log_w = log_w.data_ptr<float>();
     const AisOutputs o = alloc_ais_outputs(a, B, dim, eps0, want_base);
     fabhip_smc_args sa = {};                                   // (records: NULL until smc_outputs)
-    sa.enabled = smc_on ? 1 : 0; sa.tau = smc_on ? *smc->tau : 0.0;
+    sa.enabled = smc_on ? 1 : 0; sa.tau = smc_on ? *smc->tau : 0.0; sa.method = smc != nullptr ? (int32_t)smc->method : 0;
     auto smc_outputs = [&]() {                                 // (after the transition noise: the generator's order of draws)
         if (!smc_on) return;
         smc->u = smc_uniforms(smc->noise_r, M, eps0);
@@ -1060,9 +1061,9 @@ std::vector<Tensor> ais_run_smc(
     const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
     int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
     optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace) {
+    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, int64_t method) {
     SmcOp smc;
-    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace;
+    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.method = method;
     auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
                           noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
                           p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
@@ -1082,11 +1083,11 @@ std::vector<Tensor> ais_run_mix(
     int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
     optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
     int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, const Tensor& loc,
-    const Tensor& log_scale, const Tensor& logit, const optional<Tensor>& sel, bool enabled) {
+    const Tensor& log_scale, const Tensor& logit, const optional<Tensor>& sel, bool enabled, int64_t method) {
     MixOp mix;
     mix.enabled = enabled; mix.loc = loc; mix.log_scale = log_scale; mix.logit = logit; mix.sel = sel;
     SmcOp smc;
-    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.mix = &mix;
+    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.mix = &mix; smc.method = method;
     auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
                           noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
                           p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
@@ -1185,10 +1186,11 @@ void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t 
                    optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
                    optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision,
                    optional<double> tau, const optional<Tensor>& noise_r, bool only_resample, optional<Tensor> resampled,
-                   optional<Tensor> ess, optional<Tensor> ancestors, optional<Tensor> log_w_pre) {
+                   optional<Tensor> ess, optional<Tensor> ancestors, optional<Tensor> log_w_pre, int64_t method) {
     const int64_t B = x.size(0), M = (int64_t)betas.size() - 2;
     fabhip_smc_args sa = {};
     sa.enabled = tau.has_value() ? 1 : 0; sa.only_resample = only_resample ? 1 : 0; sa.tau = tau.has_value() ? *tau : 0.0;
+    sa.method = (int32_t)method;
     if (sa.enabled) {
         TORCH_CHECK(noise_r.has_value(), "fabhip: ais_phase_smc needs noise_r (float64 [M]) when tau is given");
         sa.u = smc_uniforms(noise_r, M, x).data_ptr<double>();
@@ -1210,7 +1212,8 @@ void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t 
 
 // The decision of the SMC step alone (fabhip_smc_decide) for samplers that step their transitions from Python:
 // (ancestors int64[n] - gather_rows takes them as they are -, resampled int32[1], ess float[1], log_w_common float[1]).
-std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, double tau, const Tensor& u) {
+// `method`: FABHIP_SMC_SYSTEMATIC (0) or FABHIP_SMC_STRATIFIED (1: the seed is the 64 bits of u).
+std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, double tau, const Tensor& u, int64_t method) {
     c10::DeviceGuard g(log_w.device());
     const int64_t n = log_w.numel();
     TORCH_CHECK(n >= 1, "fabhip: smc_decide needs at least one chain");
@@ -1222,7 +1225,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, doubl
     Tensor ws = scratch(nb, log_w);
     chk(fabhip_smc_decide(fp(log_w, "log_w"), n, nullptr, tau, u.data_ptr<double>(), anc.data_ptr<int32_t>(),
                           flag.data_ptr<int32_t>(), ess.data_ptr<float>(), common.data_ptr<float>(), nullptr, aligned(ws), nb,
-                          stream_of(log_w)),
+                          (int32_t)method, stream_of(log_w)),
         "smc_decide");
     return {anc.to(at::kLong), flag, ess, common};
 }
@@ -1445,6 +1448,20 @@ Tensor resample_systematic(const Tensor& log_w, double u0, int64_t n_samples) {
 }
 
 // seeded streaming multinomial: the 64 bits of `seed` are the C ABI's uint64 seed (order: FABHIP_ORDER_*)
+// Seeded stratified resampling indices (fabhip_resample_stratified): int64 [n_samples], non-decreasing for order = 0.
+Tensor resample_stratified(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
+    c10::DeviceGuard g(log_w.device());
+    const int64_t n = log_w.numel();
+    TORCH_CHECK(n_samples >= 1, "fabhip::resample_stratified: n_samples must be >= 1");
+    Tensor idx = at::empty({n_samples}, log_w.options().dtype(at::kLong));
+    const size_t nb = fabhip_resample_stratified_workspace_bytes(n, n_samples);
+    Tensor ws = scratch(nb, log_w);
+    chk(fabhip_resample_stratified(fp(log_w, "log_w"), n, (uint64_t)seed, n_samples, (int32_t)order, idx.data_ptr<int64_t>(),
+                                   aligned(ws), nb, stream_of(log_w)),
+        "resample_stratified");
+    return idx;
+}
+
 Tensor resample_multinomial_stream(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
     c10::DeviceGuard g(log_w.device());
     const int64_t n = log_w.numel();
@@ -1600,13 +1617,13 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
           "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
           "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
-          "Tensor? noise_r, bool want_trace) -> Tensor[]");
+          "Tensor? noise_r, bool want_trace, int method=0) -> Tensor[]");
     m.def("ais_run_mix(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
           "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
           "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
           "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
           "Tensor? noise_r, bool want_trace, Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor? sel, "
-          "bool enabled=True) -> Tensor[]");
+          "bool enabled=True, int method=0) -> Tensor[]");
     m.def("defensive_log_prob(" FLW ", Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor x, bool with_grad, "
           "int precision=0) -> (Tensor, Tensor)");
     m.def("ais_phase_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
@@ -1616,8 +1633,8 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "
           "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "
           "Tensor(q!)? base_log_w, int precision, float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
-          "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre) -> ()");
-    m.def("smc_decide(Tensor log_w, float tau, Tensor u) -> (Tensor, Tensor, Tensor, Tensor)");
+          "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre, int method=0) -> ()");
+    m.def("smc_decide(Tensor log_w, float tau, Tensor u, int method=0) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("smc_shard_pack(Tensor x, Tensor log_q, Tensor log_p, Tensor? grad_log_q, Tensor? grad_log_p, Tensor log_w, "
           "Tensor n_valid) -> Tensor");
     m.def("smc_shard_resample(Tensor gathered, int world, int rank, float tau, Tensor u, Tensor(a!) x, Tensor(b!) log_q, "
@@ -1670,6 +1687,7 @@ TORCH_LIBRARY(fabhip, m) {
     m.def("resample_multinomial(Tensor log_w, Tensor u) -> Tensor");
     m.def("resample_systematic(Tensor log_w, float u0, int n_samples) -> Tensor");
     m.def("resample_multinomial_stream(Tensor log_w, int seed, int n_samples, int order) -> Tensor");
+    m.def("resample_stratified(Tensor log_w, int seed, int n_samples, int order) -> Tensor");
     m.def("multinomial_torch(Tensor probs, Tensor u) -> Tensor");
     m.def("gather_rows(Tensor src, Tensor idx) -> Tensor");
     m.def("topk(Tensor keys, int k, bool sorted) -> Tensor");
@@ -1728,6 +1746,7 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("resample_multinomial", resample_multinomial);
     m.impl("resample_systematic", resample_systematic);
     m.impl("resample_multinomial_stream", resample_multinomial_stream);
+    m.impl("resample_stratified", resample_stratified);
     m.impl("multinomial_torch", multinomial_torch);
     m.impl("gather_rows", gather_rows);
     m.impl("topk", topk);

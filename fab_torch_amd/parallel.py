@@ -114,6 +114,19 @@ def refuse_resampling(who: str, threshold):
                           "ranks when it is built with resample_across_ranks=True)")
 
 
+def refuse_resample_method(who: str, sampler):
+    """The resampling step over ranks (fabhip_smc_shard_resample) draws systematic ancestors only: a sampler that asks for another
+    scheme is refused rather than resampled systematically - also while its `resample_threshold` is None, where the setting
+    would be inert on a plain sampler: a sampler built for resampling over ranks is refused when it is configured, not when a
+    threshold is set later."""
+    method = getattr(sampler, "resample_method", "systematic")
+    if method != "systematic":
+        from ._ops import FabhipError
+        raise FabhipError(f"{who}: resample_method={method!r} is not available with resample_across_ranks=True (the resampling "
+                          "step over ranks is systematic; refused whether or not resample_threshold is set); set "
+                          "resample_method='systematic' on the sampler")
+
+
 def refuse_mixture(who: str, sampler):
     """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_run_mix has no `partials` form and
     the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
@@ -422,6 +435,8 @@ class ShardedAnnealedImportanceSampler:
         smc_on = self.resample_across_ranks and tau is not None
         if not self.resample_across_ranks:
             refuse_resampling("ShardedAnnealedImportanceSampler", tau)
+        else:
+            refuse_resample_method("ShardedAnnealedImportanceSampler", getattr(be, "ais", None))
         if noise_r is not None and not smc_on:
             from ._ops import FabhipError
             raise FabhipError("noise_r belongs to the SMC mode over ranks: resample_across_ranks=True and a sampler with "

@@ -6,6 +6,9 @@
   device generator.
 * `resample(..., method="multinomial_stream", seed=s)`: seeded streaming multinomial - the sorted draws are generated on
   the fly from exponential spacings (a counter-based hash of the seed) and merged with the CDF; no tensor of uniforms.
+* `resample(..., method="stratified", seed=s)`: seeded stratified resampling - one hashed uniform per stratum (unbiased, every
+  count within two of its expectation, variance never above multinomial's whatever the order of the particles); the systematic
+  resampler's streaming emitter, no CDF and no tensor of uniforms in memory.
 * `multinomial_torch_compat(probs, u)`: bit-exact restatement of torch's CPU multinomial given the
   probabilities and the float64 uniforms it consumed (parity with the reference's RNG path).
 """
@@ -38,6 +41,28 @@ def systematic_indices(log_w: torch.Tensor, u0: float = None, n_samples: int = N
 STREAM_ORDERS = {"sorted": 0, "shuffled": 1}          # FABHIP_ORDER_*
 
 
+def _seed64(seed) -> int:
+    """The 64 bits of `seed` as the signed integer the ops take; None: 64 bits from torch's CPU generator."""
+    if seed is None:
+        seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (), dtype=torch.int64))
+    seed = int(seed) & ((1 << 64) - 1)
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def stratified_indices(log_w: torch.Tensor, n_samples: int = None, seed: int = None, order: str = "sorted") -> torch.Tensor:
+    """Stratified resampling indices from `(log_w, seed)` alone (include/fabhip.h: fabhip_resample_stratified): stratum k of
+    the `n_samples` equal strata of the fixed-point CDF draws its own offset, a hash of `(seed, k)`.  `order="sorted"`:
+    non-decreasing indices; `order="shuffled"`: the same indices in the seeded random order of `multinomial_stream_indices`.
+    `seed=None` draws 64 bits from torch's CPU generator; the same `(log_w, n_samples, seed, order)` gives the same indices on
+    any device.  1 <= n_samples <= 2^31 - 3."""
+    _ops.require_device(log_w, "log_w")
+    if order not in STREAM_ORDERS:
+        raise _ops.FabhipError(f"order must be 'sorted' or 'shuffled' (got {order!r})")
+    lw = log_w.detach().contiguous().float()
+    ns = lw.shape[0] if n_samples is None else int(n_samples)
+    return _ops.load().resample_stratified(lw, _seed64(seed), ns, STREAM_ORDERS[order])
+
+
 def multinomial_stream_indices(log_w: torch.Tensor, n_samples: int = None, seed: int = None,
                                order: str = "sorted") -> torch.Tensor:
     """Multinomial resampling indices from `(log_w, seed)` alone (include/fabhip.h: fabhip_resample_multinomial_stream).
@@ -49,12 +74,7 @@ def multinomial_stream_indices(log_w: torch.Tensor, n_samples: int = None, seed:
         raise _ops.FabhipError(f"order must be 'sorted' or 'shuffled' (got {order!r})")
     lw = log_w.detach().contiguous().float()
     ns = lw.shape[0] if n_samples is None else int(n_samples)
-    if seed is None:
-        seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (), dtype=torch.int64))
-    seed = int(seed) & ((1 << 64) - 1)
-    if seed >= 1 << 63:                                  # the op takes the 64 bits as a signed integer
-        seed -= 1 << 64
-    return _ops.load().resample_multinomial_stream(lw, seed, ns, STREAM_ORDERS[order])
+    return _ops.load().resample_multinomial_stream(lw, _seed64(seed), ns, STREAM_ORDERS[order])
 
 
 def multinomial_torch_compat(probs: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
@@ -69,9 +89,11 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 def resample(x_or_point: Union[Point, torch.Tensor], log_w: torch.Tensor, method: str = "multinomial", seed: int = None):
     """Resample points according to the log weights (same call shape as the reference).  `seed` belongs to
-    `method="multinomial_stream"` (the other methods draw from torch's generators)."""
+    `method="multinomial_stream"` and `method="stratified"` (the other methods draw from torch's generators)."""
     if method == "multinomial_stream":
         idx = multinomial_stream_indices(log_w, seed=seed)
+    elif method == "stratified":
+        idx = stratified_indices(log_w, seed=seed)
     else:
         idx = multinomial_indices(log_w) if method == "multinomial" else systematic_indices(log_w)
     if isinstance(x_or_point, Point):

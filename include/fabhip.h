@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 221
+#define FABHIP_ABI_VERSION 222
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -613,7 +613,13 @@ int fabhip_ais_phase(const fabhip_ais_args* args, int32_t phases, int32_t j_begi
  *              max + log(sum W 2^-36 / n0), so that logsumexp(log_w) - and with it log Z - is what it was;
  *   else the step is the identity.
  * Decided and executed on the device: the launch sequence does not depend on the outcome, the host never waits.
- * `enabled` == 0 (or a NULL fabhip_smc_args): the plain call, launch for launch.  The outputs may each be NULL. */
+ * `enabled` == 0 (or a NULL fabhip_smc_args): the plain call, launch for launch.  The outputs may each be NULL.
+ * `method` = FABHIP_SMC_STRATIFIED: the decision is the same, the ancestors are the stratified resampler's
+ * (fabhip_resample_stratified below) for n_samples = n0 and seed = the 64 bits of the float64 u[j - 1] read as an unsigned
+ * integer (u outside [0, 1): taken as 0.0, i.e. seed 0) - still one float64 per transition.  Any other value than the two
+ * below: FABHIP_EINVAL. */
+#define FABHIP_SMC_SYSTEMATIC 0
+#define FABHIP_SMC_STRATIFIED 1
 typedef struct {
     int32_t enabled;
     int32_t only_resample;    /* != 0: run the resampling steps of j_begin .. j_end WITHOUT their transitions (tests read the
@@ -625,6 +631,7 @@ typedef struct {
     float* ess;               /* device [M]: the ess the decision saw                                                          */
     int32_t* ancestors;       /* device [M][B]: row k of the point came from row ancestors[j-1][k] (identity: no resampling)   */
     float* log_w_pre;         /* device [M][B]: log_w as the decision saw it                                                   */
+    int32_t method;           /* FABHIP_SMC_SYSTEMATIC (0: what a zero-initialised struct has) or FABHIP_SMC_STRATIFIED          */
 } fabhip_smc_args;
 
 /* fabhip_ais_workspace_bytes + the scratch of the resampling step (CDF, ancestors, flag) */
@@ -666,11 +673,12 @@ int fabhip_defensive_log_prob(const fabhip_flow* flow, const fabhip_defensive_ar
 
 /* The decision alone, for samplers that step their transitions themselves (the generic plug-in path): ancestors [B] (identity
  * where nothing is resampled and beyond *n_ptr rows), resampled [1], log_w_common [1] (the value every log_w[:n0] takes when
- * resampled[0] == 1) are required; ess [1] and log_w_pre [B] may be NULL.  n_ptr NULL: all B rows.  u: device, one double. */
+ * resampled[0] == 1) are required; ess [1] and log_w_pre [B] may be NULL.  n_ptr NULL: all B rows.  u: device, one double.
+ * method: FABHIP_SMC_SYSTEMATIC or FABHIP_SMC_STRATIFIED (fabhip_smc_args.method), anything else FABHIP_EINVAL. */
 size_t fabhip_smc_workspace_bytes(int64_t B);
 int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
                       int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
-                      size_t workspace_bytes, fabhip_stream_t stream);
+                      size_t workspace_bytes, int32_t method, fabhip_stream_t stream);
 
 /* SMC mode over SHARDED chains (fab_torch_amd/parallel.py: resample_across_ranks; definition: tests/smc_shard_spec.py).
  * R ranks hold b rows each, the first n_r = n_valid[0] of them live; the global live order is the ranks' live rows in rank
@@ -838,6 +846,31 @@ int fabhip_resample_systematic(const float* log_w, int64_t n, double u0, int64_t
 size_t fabhip_resample_stream_workspace_bytes(int64_t n, int64_t n_samples);
 int fabhip_resample_multinomial_stream(const float* log_w, int64_t n, uint64_t seed, int64_t n_samples, int32_t order,
                                        int64_t* idx, void* workspace, size_t workspace_bytes, fabhip_stream_t stream);
+/* Seeded stratified resampler: one independent uniform per stratum (the systematic resampler draws one for all of them), from
+ * (log_w, seed) alone.  Unbiased, every count within two of n_samples W_j / total, variance never above multinomial
+ * resampling's and - unlike the systematic resampler's - independent of the order of the particles.  The definition is the
+ * project's own (tests/resample_stratified_spec.py restates it; the device follows it bit for bit on any launch geometry):
+ *   W, C, total: the fixed-point weights and CDF above (non-finite rows weigh 0); total == 0: every index is n - 1.
+ *   F = 62 - bit_length(total), S = floor(total 2^F / n_samples): the systematic resampler's stratum map.
+ *   stratum k = 0 .. n_samples - 1:  h_k = the splitmix64 finaliser r above for i = k (the counter is the stratum number),
+ *     U_k = (h_k * S) >> 64, the high half of the 128-bit product, in [0, S - 1];  t_k = (k S + U_k) >> F;
+ *     idx_k = first j with C_j > t_k   (k S + U_k < 2^62: 64-bit integers throughout; non-decreasing in k).
+ *   Inverse evaluated per CDF value (no CDF and no thresholds in HBM): with B = C_j << F and q = min(floor(B / S), n_samples),
+ *     K(C_j) = q + [q < n_samples and q S + U_q < B], weight j owns the strata [K(C_{j-1}), K(C_j)).
+ *   order = FABHIP_ORDER_SORTED returns idx; FABHIP_ORDER_SHUFFLED returns out[k] = idx[pi(k)], pi the keyed bijection of the
+ *   streaming multinomial resampler above (same keys: the low 32 bits of r for i = 2^40 + j).
+ * Limits: n >= 1, 1 <= n_samples <= FABHIP_STRATIFIED_MAX_SAMPLES = 2^31 - 3.  FABHIP_EINVAL for n < 1, n_samples < 1, n_samples
+ * beyond the limit, an unknown order, a NULL pointer or a workspace that is not 256-byte aligned; FABHIP_ENOSPC for a workspace
+ * smaller than fabhip_resample_stratified_workspace_bytes(n, n_samples) (0 for arguments the call refuses).  All of it is
+ * checked before any launch and without touching a device.  The caller owns log_w [n], idx [n_samples] and the workspace
+ * (device memory); nothing is allocated, nothing synchronises, every launch goes to `stream`.
+ * Launches: maximum (2), wave-tile sums, block prefix + stratum map, emit, grid-wide fill of runs >= 32768 (n_samples >= 32768
+ * only), shuffle (order = shuffled only).  Traffic, order = sorted: the systematic call's 12 n + 8 n_samples bytes; one hash per
+ * weight, none per draw. */
+#define FABHIP_STRATIFIED_MAX_SAMPLES ((int64_t)((1ll << 31) - 3))
+size_t fabhip_resample_stratified_workspace_bytes(int64_t n, int64_t n_samples);
+int fabhip_resample_stratified(const float* log_w, int64_t n, uint64_t seed, int64_t n_samples, int32_t order, int64_t* idx,
+                               void* workspace, size_t workspace_bytes, fabhip_stream_t stream);
 /* dst[k][:] = src[idx[k]][:]  (Point.__getitem__ / tensor indexing used by resample) */
 int fabhip_gather_rows(const float* src, const int64_t* idx, float* dst, int64_t n_out, int64_t row_len,
                        fabhip_stream_t stream);

@@ -11,7 +11,11 @@ off and tau = 0.5, with the untrained seeded flow of the benchmark.
 Resampling step alone (HIP events around CALLS steps, REPEATS repeats, us per step): the sharded step - smc_shard_pack +
 smc_shard_resample on an emulated gathered buffer of 8 ranks x 2048 chains (the collective itself is NOT in it) - next to the
 single-device step (decision + gather + copy-back, ais_phase_smc with only_resample) at 2048 and at 16384 chains, each firing
-(tau = 1.5) and not firing (tau = 0).  One JSON line."""
+(tau = 1.5) and not firing (tau = 0).  One JSON line.
+
+METHOD=systematic|stratified in the environment chooses the sampler's `resample_method` for all of it (the sharded step is
+systematic only and is left out for stratified).  QUICK_TAU=0.5: only the call's timing at that threshold, 1024 and 2048 chains,
+for BOTH methods alternating - the comparison of the two schemes."""
 import json
 import os
 import sys
@@ -25,18 +29,20 @@ from bench import build_flow_state, _lib_srchash      # the bench's seeded headl
 DEV = "cuda"
 D, M, L = 32, 8, 5
 CALLS, REPEATS, SEEDS = int(os.environ.get("CALLS", 200)), int(os.environ.get("REPEATS", 5)), int(os.environ.get("SEEDS", 8))
+METHOD = os.environ.get("METHOD", "systematic")
 flow = build_flow_state(0).to(DEV).requires_grad_(False)
 target = fa.ManyWellEnergy(D)
 
 
-def sampler(tau, p_target=False, tune=True, eps=0.1):
+def sampler(tau, p_target=False, tune=True, eps=0.1, method=None):
     hmc = fa.HamiltonianMonteCarlo(M, D, flow.log_prob, target.log_prob, alpha=2.0, p_target=p_target, epsilon=eps, L=L,
                                    eval_mode=not tune).to(DEV)
-    return fa.AnnealedImportanceSampler(flow, target.log_prob, hmc, p_target, 2.0, M, resample_threshold=tau)
+    return fa.AnnealedImportanceSampler(flow, target.log_prob, hmc, p_target, 2.0, M, resample_threshold=tau,
+                                        resample_method=METHOD if method is None else method)
 
 
-def time_setting(B, tau, prefetch):
-    ais = sampler(tau)
+def time_setting(B, tau, prefetch, method=None):
+    ais = sampler(tau, method=method)
     ais.prefetch = prefetch
     torch.manual_seed(1)
     for _ in range(100):
@@ -100,7 +106,8 @@ def single_device_step(B, tau):
     nr = torch.rand(M, dtype=torch.float64, device=DEV)
     args = (*be._common(st), 0, 1, 1, st["eps0"], st["noise_a"], st["noise_b"], *operator_slots(be.op)[1][:7], False, st["x"],
             st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], None, None, None, None, None, None,
-            None, _ops.precision_of(flow), float(tau), nr, True, None, None, None, None)
+            None, _ops.precision_of(flow), float(tau), nr, True, None, None, None, None,
+            fa.ais.RESAMPLE_METHODS[METHOD])
     return _event_us(lambda: be.ops.ais_phase_smc(*args))
 
 
@@ -118,7 +125,13 @@ def sharded_step(R, b, tau):
 
 
 out = {"config": f"ManyWell-{D}, RealNVP 10x(16-320-320-32), M={M}, HMC L={L}", "lib_srchash": _lib_srchash()[:12],
-       "calls": CALLS, "repeats": REPEATS}
+       "calls": CALLS, "repeats": REPEATS, "method": METHOD}
+if os.environ.get("QUICK_TAU"):
+    tau = float(os.environ["QUICK_TAU"])
+    for B in (1024, 2048):
+        out[f"B{B}"] = {f"{m}_{i}": time_setting(B, tau, False, method=m) for i in range(2) for m in ("systematic", "stratified")}
+    print(json.dumps(out))
+    sys.exit(0)
 for B in (1024, 2048):
     row = {"off": time_setting(B, None, True), "off_noprefetch": time_setting(B, None, False),
            "tau_0": time_setting(B, 0.0, False), "tau_1.5": time_setting(B, 1.5, False)}
@@ -128,7 +141,8 @@ for B in (1024, 2048):
     out[f"B{B}"] = row
 out["log_Z_error_B1024"] = {"off": log_z_errors(1024, None), "tau_0.5": log_z_errors(1024, 0.5)}
 out["resampling_step_us"] = {
-    f"tau_{tau}": {"sharded_R8_b2048": sharded_step(8, 2048, tau), "single_B2048": single_device_step(2048, tau),
+    f"tau_{tau}": {**({"sharded_R8_b2048": sharded_step(8, 2048, tau)} if METHOD == "systematic" else {}),
+                   "single_B2048": single_device_step(2048, tau),
                    "single_B16384": single_device_step(16384, tau)} for tau in (1.5, 0.0)}
 out["resampling_step_us"]["state_payload_bytes_per_rank"] = {"sent": (2048 + 1) * (3 * D + 4) * 4, "received": 8 * (2048 + 1) * (3 * D + 4) * 4}
 print(json.dumps(out))
