@@ -123,8 +123,9 @@ SYMBOLS = [
     "fabhip_smc_shard_workspace_bytes", "fabhip_smc_shard_pack", "fabhip_smc_shard_resample",
     "fabhip_ais_run_mix", "fabhip_ais_phase_mix", "fabhip_defensive_log_prob",
     "fabhip_resample_stratified_workspace_bytes", "fabhip_resample_stratified",
+    "fabhip_next_beta", "fabhip_log_w_first",
 ]
-ABI_VERSION = 222          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 223          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -162,6 +163,8 @@ def _declare(lib):
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]
     lib.fabhip_smc_decide.argtypes = [vp, i64, vp, dbl, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
+    lib.fabhip_next_beta.argtypes = [vp, vp, vp, i64, vp, dbl, dbl, i32, dbl, i32, vp, vp]
+    lib.fabhip_log_w_first.argtypes = [vp, vp, i64, Anneal, vp, vp]
     lib.fabhip_smc_shard_workspace_bytes.restype = sz
     lib.fabhip_smc_shard_workspace_bytes.argtypes = [i32, i64]
     lib.fabhip_smc_shard_pack.argtypes = [C.POINTER(Point), vp, vp, i64, i32, vp, vp]

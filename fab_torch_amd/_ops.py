@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 222          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 223          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM = 1, 2
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -257,6 +257,10 @@ def _register_fakes():
     def _(log_w, tau, u, method=0):
         return (log_w.new_empty((log_w.shape[0],), dtype=torch.int64), log_w.new_empty((1,), dtype=torch.int32),
                 log_w.new_empty((1,)), log_w.new_empty((1,)))
+
+    @rf("fabhip::next_beta")
+    def _(log_w, log_q, log_p, n_valid, beta, alpha, p_target, rho, iters=24):
+        return log_w.new_empty((4,), dtype=torch.float64)
 
     @rf("fabhip::resample_multinomial")
     def _(log_w, u):

@@ -80,8 +80,56 @@ def _check_threshold(tau):
     return float(tau)
 
 
+def check_schedule(values, M: int, what: str = "distribution_spacing_type") -> torch.Tensor:
+    """A caller's annealing schedule as the float64 `B_space` tensor: M + 2 finite, non-decreasing values from 0 to 1 (repeated
+    entries are legal: the increment of such a step is skipped)."""
+    if torch.is_tensor(values):
+        if values.dtype != torch.float64:
+            raise _ops.FabhipError(f"{what}: a schedule given as a tensor must be float64 (got {values.dtype})")
+        b = values.detach().cpu().numpy()
+    else:
+        try:
+            b = np.asarray(values, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise _ops.FabhipError(f"{what} must be 'linear', 'geometric', 'adaptive' or a sequence of {int(M) + 2} numbers "
+                                   f"(got {values!r})") from e
+    if b.shape != (int(M) + 2,):
+        raise _ops.FabhipError(f"{what}: a schedule needs n_intermediate_distributions + 2 = {int(M) + 2} values, got shape "
+                               f"{tuple(b.shape)}")
+    if not np.isfinite(b).all() or b[0] != 0.0 or b[-1] != 1.0 or (np.diff(b) < 0).any():
+        raise _ops.FabhipError(f"{what}: a schedule must be finite and non-decreasing, start at 0 and end at 1 (got {b.tolist()})")
+    return torch.tensor(b, dtype=torch.float64)
+
+
+def check_ess_decay(rho) -> float:
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not 0.0 < float(rho) < 1.0:
+        raise _ops.FabhipError(f"ess_decay must be a number in (0, 1): the fraction of the current ESS a step keeps (got {rho!r})")
+    return float(rho)
+
+
+class AdaptiveDecision(NamedTuple):
+    """One decision of an adaptive schedule: made after transition `step` (0: after the chain initialisation) at `beta`."""
+    step: int
+    beta: float
+    beta_next: float          # the decision's own value (a forced schedule may have used another)
+    ess0: float
+    ess_choice: float
+    evaluations: int
+    floor: bool
+    inputs: Optional[tuple]   # (log_w, log_q, log_p) as the kernel saw them (`trace=True`), else None
+
+
+NEXT_BETA_ITERS = 24          # K of fabhip_next_beta: the schedule is resolved to (1 - beta) 2^-24
+
+
 class AnnealedImportanceSampler:
-    """`resample_threshold` (SMC mode, default None = plain AIS): before every transition the ESS of the current log-weights is
+    """`distribution_spacing_type`: "linear" / "geometric" (the reference's), a schedule of the caller's (sequence, array or
+    float64 tensor of M + 2 non-decreasing values from 0 to 1), or "adaptive": every temperature is chosen on the device from
+    the weights (fabhip_next_beta: the largest step that keeps `ess_decay` of the current ESS, by bisection), the call is
+    stepped transition by transition with one 32-byte read each, `last_betas` holds the schedule the call chose and `B_space`
+    the linear one as a nominal value.
+
+    `resample_threshold` (SMC mode, default None = plain AIS): before every transition the ESS of the current log-weights is
     computed on the device; below the threshold the chains are resampled in proportion to their weights (systematic, on the
     fixed-point CDF of `resample_systematic`) and continue with equal weights whose logsumexp is unchanged, so `log_Z`, the FAB
     loss and the buffer see an ordinary `(point, log_w)`.  > 1: before every transition; 0: never (the decision still runs).
@@ -93,12 +141,15 @@ class AnnealedImportanceSampler:
 
     def __init__(self, base_distribution, target_log_prob, transition_operator: TransitionOperator,
                  p_target: bool, alpha: Optional[float] = None, n_intermediate_distributions: int = 1,
-                 distribution_spacing_type: str = "linear", resample_threshold: Optional[float] = None,
-                 resample_method: str = "systematic"):
+                 distribution_spacing_type="linear", resample_threshold: Optional[float] = None,
+                 resample_method: str = "systematic", ess_decay: float = 0.7):
         if not p_target:
             assert alpha is not None, "Must specify alpha if AIS target is not p."
         self.resample_threshold = resample_threshold
         self.resample_method = resample_method
+        self.ess_decay = ess_decay        # adaptive schedules only: the fraction of the current ESS a step keeps
+        self.last_betas = None            # float64 [M + 2]: the schedule the last adaptive call chose
+        self.last_adaptive = None         # its decisions (AdaptiveDecision)
         self.last_smc = None              # (resampled [M], ess [M], ancestors [M, B], log_w_pre [M, B]) of the last fused call
         self.base_distribution = base_distribution
         self.target_log_prob = target_log_prob
@@ -127,6 +178,35 @@ class AnnealedImportanceSampler:
     def resample_method(self, method):
         self.__dict__["_resample_method"] = check_resample_method(method)
 
+    @property
+    def ess_decay(self) -> float:
+        return self.__dict__.get("_ess_decay", 0.7)
+
+    @ess_decay.setter
+    def ess_decay(self, rho):
+        self.__dict__["_ess_decay"] = check_ess_decay(rho)
+
+    @property
+    def adaptive(self) -> bool:
+        t = self.__dict__.get("distribution_spacing_type")
+        return isinstance(t, str) and t == "adaptive"
+
+    def _refuse_adaptive(self, what: str, instead: str):
+        if self.adaptive:
+            raise _ops.FabhipError(f"distribution_spacing_type='adaptive' is not available for {what}: {instead}")
+
+    def _refuse_adaptive_routes(self):
+        """The routes an adaptive schedule does not run on, refused by name before any op is reached."""
+        if not self.adaptive:
+            return
+        fixed = "set distribution_spacing_type to 'linear', 'geometric' or a schedule of your own"
+        if self._spline_parts() is not None:
+            self._refuse_adaptive("the fused spline-flow call", fixed + " (the last_betas of a RealNVP run, for instance)")
+        if isinstance(self.base_distribution, DefensiveMixtureDistribution):
+            self._refuse_adaptive("a DefensiveMixtureDistribution base (the call made in pieces refuses the mixture)", fixed)
+        if not self.is_native:
+            self._refuse_adaptive("the generic path (plug-in base distribution / target / transition operator)", fixed)
+
     def _refuse_resampling(self, what: str):
         if self.resample_threshold is not None:
             raise _ops.FabhipError(f"resample_threshold={self.resample_threshold} (SMC mode) is not available for {what}: "
@@ -136,21 +216,25 @@ class AnnealedImportanceSampler:
         info = self._logging_info._asdict()
         if self.resample_threshold is not None and self.__dict__.get("_smc_info") is not None:
             info.update(self._smc_info)                     # n_resampled, ess_min_in_chain of the last logged call
+        if self.adaptive and self.__dict__.get("_adaptive_info") is not None:
+            info.update(self._adaptive_info)                # beta_1, n_steps_to_beta_one, n_bisect_floor of the last call
         info.update(self.transition_operator.get_logging_info())
         return info
 
-    def setup_distribution_spacing(self, distribution_spacing_type: str, n_intermediate_distributions: int
+    def setup_distribution_spacing(self, distribution_spacing_type, n_intermediate_distributions: int
                                    ) -> torch.Tensor:
         assert n_intermediate_distributions > 0
+        if not isinstance(distribution_spacing_type, str):                       # a schedule of the caller's
+            return check_schedule(distribution_spacing_type, n_intermediate_distributions)
         if distribution_spacing_type == "geometric":
             n_lin = int(n_intermediate_distributions / 4)
             n_geo = n_intermediate_distributions - n_lin - 1
             B_space = np.concatenate([np.linspace(0, 0.01, n_lin + 2)[:-1], np.geomspace(0.01, 1, n_geo + 2)])
-        elif distribution_spacing_type == "linear":
+        elif distribution_spacing_type in ("linear", "adaptive"):                # (adaptive: the nominal value of B_space)
             B_space = np.linspace(0.0, 1.0, n_intermediate_distributions + 2)
         else:
             raise Exception(f"distribution spacing incorrectly specified: '{distribution_spacing_type}',"
-                            f"options are 'geometric' or 'linear'")
+                            f"options are 'geometric', 'linear', 'adaptive' or a sequence of M + 2 values")
         assert B_space.shape == (self.n_intermediate_distributions + 2,)
         return torch.tensor(B_space)
 
@@ -191,6 +275,7 @@ class AnnealedImportanceSampler:
         """`run` for the spline family: ONE op call (torch.ops.fabhip.spline_ais_run).  `eps0` / `u0` [B, D]: the normal /
         uniform draws of the flow's base sample."""
         self._refuse_resampling("the fused spline-flow call")
+        self._refuse_adaptive_routes()
         flow, target = self._spline_parts()
         op = self.transition_operator
         head = self._call_head(flow, target, _ops.TRANSITION_HMC)[:-1]       # (HMC only: the spline op has no transition slot)
@@ -207,8 +292,10 @@ class AnnealedImportanceSampler:
         return Point(x, lq, lp, gq, gp), log_w, n_valid, stats, base_x, base_lw
 
     def run(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None, noise_r=None,
-            trace: bool = False, sel=None):
-        """(`sel` [B] uniforms in [0, 1): the branch draws of a DefensiveMixtureDistribution base - chain i starts from the flow iff
+            trace: bool = False, sel=None, force_betas=None):
+        """(`force_betas` [M + 2], adaptive schedules only: the call runs on this schedule; the decisions still run and are
+        recorded in `last_adaptive` - with `trace` together with the log_w, log_q, log_p each of them saw.)
+        (`sel` [B] uniforms in [0, 1): the branch draws of a DefensiveMixtureDistribution base - chain i starts from the flow iff
         sel_i < sigmoid(mixture_logit); absent: drawn on the device after eps0 and before the transition noise.)
         (`noise_r` [M] float64: the uniforms of the resampling steps, SMC mode only; `trace`: keep the ancestors and the
         log-weights every decision saw in `last_smc`.)
@@ -216,10 +303,18 @@ class AnnealedImportanceSampler:
         Enqueue one AIS call; returns device tensors (Point fields sized [batch_size], log_w, n_valid[2],
         stats[16], base_x, base_log_w) without synchronising.  `want_base`: also return the chains' starting points
         after the "chain init" filtering and their log p - log q (generate_eval_data, ais.py:152-166)."""
+        self._refuse_adaptive_routes()
+        if force_betas is not None and not self.adaptive:
+            raise _ops.FabhipError("force_betas belongs to distribution_spacing_type='adaptive'; a fixed schedule is passed as "
+                                   "distribution_spacing_type itself")
         if self._spline_parts() is not None:
             return self._run_spline(batch_size, eps0, noise_a, noise_b, want_base, u0=u0)
         if u0 is not None:
             raise _ops.FabhipError("u0 (uniform base draws) belongs to the fused spline-flow call; a RealNVP takes eps0 only")
+        if self.adaptive:
+            if sel is not None:
+                raise _ops.FabhipError("sel (branch uniforms) belongs to a DefensiveMixtureDistribution base distribution")
+            return self._run_adaptive(batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas)
         ops = _ops.load()
         flow, target = self._native_parts()
         kind, slots = operator_slots(self.transition_operator)
@@ -295,14 +390,15 @@ class AnnealedImportanceSampler:
         """`alpha` as the ops take it (their `float alpha` is not read when the AIS target is p)."""
         return float(self.alpha) if self.alpha is not None else 0.0
 
-    def _call_head(self, flow, target, transition) -> tuple:
+    def _call_head(self, flow, target, transition, betas=None) -> tuple:
         """The leading arguments of ais_run / ais_run_smc / ais_phase / ais_sharded_tuned: flow image, target, betas, alpha,
-        p_target, transition kind."""
+        p_target, transition kind.  (`betas`: a per-call list in place of B_space - the stepped adaptive driver's.)"""
         op = self.transition_operator
         if bool(op.p_target) != bool(self.p_target) or (not self.p_target and op.alpha != self.alpha):
             # the reference keeps the two in sync through FABModel.set_ais_target (core.py:102-110)
             raise _ops.FabhipError("AIS and transition operator disagree on p_target / alpha")
-        return (*flow.native(), *target.native_target(), self._betas(), self._alpha_arg, bool(self.p_target), transition)
+        return (*flow.native(), *target.native_target(), self._betas() if betas is None else betas, self._alpha_arg,
+                bool(self.p_target), transition)
 
     def new_phase_state(self, b, eps0=None, noise_a=None, noise_b=None, draw_noise: bool = True, slab: bool = False) -> dict:
         """The caller-owned tensors of one AIS call made in pieces (`enqueue_phase`): Point fields, log_w, the 18-word
@@ -348,6 +444,85 @@ class AnnealedImportanceSampler:
                               st["noise_b"], *s[:7], s.tune if tune is None else bool(tune), st["x"], st["lq"], st["lp"],
                               st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], partials, *log, None, None,
                               _ops.precision_of(flow))
+
+    # ---- adaptive schedule: the call stepped transition by transition, the next temperature chosen on the device ---------------
+    def _run_adaptive(self, batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas):
+        """`run` with distribution_spacing_type="adaptive" (definition: tests/adaptive_spec.py).  FABHIP_AIS_INIT at beta_1 := 0,
+        then per step: [resampling step +] transition j at beta_j through the phase op (betas[j] = betas[j + 1] = beta_j: no
+        increment inside), fabhip_next_beta on the new point, ONE 32-byte read, the increment (fabhip_log_w_update: the fused
+        kernels' expression; the first weight through fabhip_log_w_first: the chain initialisation's).  FABHIP_AIS_FINISH last.
+        Once beta has reached 1 the remaining transitions run on the target without a decision or an increment."""
+        ops = _ops.load()
+        flow, target = self._native_parts()
+        kind, s = operator_slots(self.transition_operator)
+        B, M = int(batch_size), self.n_intermediate_distributions
+        alpha, p_target, rho, prec = self._alpha_arg, bool(self.p_target), self.ess_decay, _ops.precision_of(flow)
+        tau = self.resample_threshold
+        forced = None if force_betas is None else check_schedule(force_betas, M, "force_betas").tolist()
+        st = self.new_phase_state(B, eps0, noise_a, noise_b)
+        dev = st["x"].device
+        smc = ()
+        if noise_r is not None and tau is None:
+            raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
+        if tau is not None:
+            noise_r = torch.rand(M, dtype=torch.float64, device=dev) if noise_r is None else check_noise_r(noise_r, M)
+            rec = (torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.float32, device=dev),
+                   torch.zeros((M, B), dtype=torch.int32, device=dev) if trace else None,
+                   torch.zeros((M, B), dtype=torch.float32, device=dev) if trace else None)
+            smc = (tau, noise_r, False, *rec, RESAMPLE_METHODS[self.resample_method])
+        base = (torch.empty_like(st["x"]), torch.empty_like(st["log_w"])) if want_base else (None, None)
+
+        def phase(phases, j0, j1, betas, base=(None, None)):
+            args = (*self._call_head(flow, target, kind, betas), phases, j0, j1, st["eps0"], st["noise_a"], st["noise_b"],
+                    *s[:8], st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], None,
+                    *s[8:], *base, prec)
+            if smc and j0 <= j1:
+                ops.ais_phase_smc(*args, *smc)
+            else:
+                ops.ais_phase(*args)
+
+        def at(j, beta):                         # the per-call betas of transition j: betas[j] = betas[j + 1] = beta
+            b = [0.0] * (M + 2)
+            b[j] = b[j + 1] = float(beta)
+            return b
+
+        decisions = []
+
+        def decide(step, beta):
+            out = ops.next_beta(st["log_w"], st["lq"], st["lp"], st["n_valid"], float(beta), alpha, p_target, rho, NEXT_BETA_ITERS)
+            seen = (st["log_w"].clone(), st["lq"].clone(), st["lp"].clone()) if trace else None
+            v = _ops._read_small(out).tolist()                                   # the step's one device->host read
+            decisions.append(AdaptiveDecision(step, float(beta), v[0], v[1], v[2], int(v[3]) & 0xffff, int(v[3]) >= 65536, seen))
+            return v[0]
+
+        phase(1, 1, 0, at(0, 0.0), base)                                         # FABHIP_AIS_INIT with betas[1] = 0
+        b1 = decide(0, 0.0)
+        chosen = [0.0, forced[1] if forced is not None else b1]
+        if chosen[1] != 0.0:
+            ops.log_w_first(st["lq"], st["lp"], chosen[1], alpha, p_target, st["log_w"])
+        for j in range(1, M + 1):
+            bj = chosen[j]
+            phase(0, j, j, at(j, bj))
+            nxt = 1.0
+            if j < M:
+                nxt = decide(j, bj) if bj < 1.0 else 1.0
+                if forced is not None:
+                    nxt = forced[j + 1]
+            if nxt != bj:
+                ops.log_w_update(st["lq"], st["lp"], bj, nxt, alpha, p_target, st["log_w"])
+            chosen.append(nxt)
+        phase(2, 1, 0, at(M, chosen[M]))                                         # FABHIP_AIS_FINISH
+        self.last_betas = torch.tensor(chosen, dtype=torch.float64)
+        self.last_adaptive = decisions
+        self.__dict__["_adaptive_info"] = {
+            "beta_1": float(chosen[1]), "n_steps_to_beta_one": int(next(i for i, b in enumerate(chosen) if b >= 1.0)),
+            "n_bisect_floor": int(sum(d.floor for d in decisions))}
+        if tau is not None:
+            empty = torch.empty(0, device=dev)
+            self.last_smc = (rec[0], rec[1], rec[2] if trace else empty.int(), rec[3] if trace else empty)
+        hmc = kind == _ops.TRANSITION_HMC
+        point = Point(st["x"], st["lq"], st["lp"], st["gq"] if hmc else None, st["gp"] if hmc else None)
+        return point, st["log_w"], st["n_valid"], st["stats"], base[0], base[1]
 
     def _pf_take(self, key):
         """The prefetched piece made for `key`, if the generator is where the prefetch left it; else it is dropped (and, when only
@@ -398,6 +573,8 @@ class AnnealedImportanceSampler:
     def perform_transition(self, x_new: Point, log_w: torch.Tensor, j: int):
         """ais.py:90-105: one MCMC transition towards the j-th intermediate distribution + the log-weight increment
         (skipped when beta does not change).  The fused call does the same for all j inside `fabhip_ais_run`."""
+        self._refuse_adaptive("perform_transition (one transition of a FIXED schedule)",
+                              "run the whole call (sample_and_log_weights / run), or give the sampler a schedule of your own")
         beta, beta_next = float(self.B_space[j]), float(self.B_space[j + 1])
         log_w = log_w.detach().clone().contiguous()
         x_new = self.transition_operator.transition(x_new, j, beta, log_w=log_w if beta_next != beta else None,
@@ -508,14 +685,15 @@ class AnnealedImportanceSampler:
 
     def sample_and_log_weights(self, batch_size: int, logging: bool = True, eps0=None, noise_a=None, noise_b=None,
                                u0=None, noise_r=None, sel=None) -> Tuple[Point, torch.Tensor]:
+        self._refuse_adaptive_routes()
         fused_spline = self._spline_parts() is not None
-        smc_on = self.resample_threshold is not None
+        smc_on = self.resample_threshold is not None or self.adaptive          # (both step outside the plain phase op's pieces)
         mix_on = self._mixture() is not None and self.is_native
         if sel is not None and not mix_on:
             raise _ops.FabhipError("sel (branch uniforms) belongs to the fused call over a DefensiveMixtureDistribution base")
         if fused_spline:
             self._refuse_resampling("the fused spline-flow call")
-        if noise_r is not None and not smc_on:
+        if noise_r is not None and self.resample_threshold is None:
             raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
         if u0 is not None and not fused_spline:               # (it used to be dropped silently)
             raise _ops.FabhipError("u0 (uniform base draws) belongs to the fused spline-flow call: this sampler's base "
@@ -568,6 +746,7 @@ class AnnealedImportanceSampler:
         concatenates on the CPU after a `.cpu()` per batch); the returned tensors live on the GPU.  Generic plug-ins
         (e.g. the spline flow): the reference's loop per batch through `_sample_generic`."""
         assert outer_batch_size % inner_batch_size == 0
+        self._refuse_adaptive_routes()
         n_batches = outer_batch_size // inner_batch_size
         B = inner_batch_size
         if not self.is_native and self._spline_parts() is None:

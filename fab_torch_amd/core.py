@@ -30,8 +30,9 @@ class FABModel:
     def __init__(self, flow, target_distribution, n_intermediate_distributions: int, alpha: float = 2.,
                  transition_operator: Optional[TransitionOperator] = None, ais_distribution_spacing: str = "linear",
                  loss_type: Optional[str] = None, use_ais: bool = True, ais_resample_threshold: Optional[float] = None,
-                 ais_resample_method: str = "systematic"):
+                 ais_resample_method: str = "systematic", ais_ess_decay: float = 0.7):
         assert loss_type in SUPPORTED_LOSSES
+        self.ais_ess_decay = ais_ess_decay                         # adaptive schedules (ais_distribution_spacing="adaptive")
         self.ais_resample_threshold = ais_resample_threshold       # SMC mode of the sampler (ais.py), None: plain AIS
         self.ais_resample_method = check_resample_method(ais_resample_method)   # "systematic" / "stratified" ancestors of that mode
         if loss_type in EXPERIMENTAL_LOSSES:               # same refusal as the reference (core.py:50-51)
@@ -58,7 +59,8 @@ class FABModel:
             n_intermediate_distributions=self.n_intermediate_distributions,
             distribution_spacing_type=self.ais_distribution_spacing,
             resample_threshold=getattr(self, "ais_resample_threshold", None),
-            resample_method=getattr(self, "ais_resample_method", "systematic"))
+            resample_method=getattr(self, "ais_resample_method", "systematic"),
+            ess_decay=getattr(self, "ais_ess_decay", 0.7))
 
     def parameters(self):
         return self.flow.parameters()

@@ -184,6 +184,16 @@ __global__ void k_gen_logw_update(long n, const float* __restrict__ lq, const fl
         log_w[i] = log_w[i] + ((nx.c_q * lq[i] + nx.c_p * lp[i]) - (c.c_q * lq[i] + c.c_p * lp[i]));
 }
 
+// The first weight of a chain whose initialisation ran at beta = 0 (adaptive schedules: fabhip_next_beta chooses beta_1 from
+// the weights that start left): log_w = log_q - log_q0 there, a difference of two float32 values of the same density that is
+// exact (Sterbenz), so log_q0 = log_q - log_w is recovered exactly and the weight at beta_1 is the chain initialisation's own
+// expression  pi_{beta_1}(point) - log_q0  with its single rounding - not the two adds of an increment.
+__global__ void k_gen_logw_first(long n, const float* __restrict__ lq, const float* __restrict__ lp, fabhip_anneal nx,
+                                 float* __restrict__ log_w) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        log_w[i] = (nx.c_q * lq[i] + nx.c_p * lp[i]) - (lq[i] - log_w[i]);
+}
+
 __global__ void k_gen_met_propose(long n, const float* __restrict__ x, const float* __restrict__ noise,
                                   const float* __restrict__ scale_ptr, float* __restrict__ xn) {
     const float sc = *scale_ptr;
@@ -361,6 +371,14 @@ int fabhip_log_w_update(const float* log_q, const float* log_p, int64_t n, fabhi
     if (n == 0) return FABHIP_OK;
     hipLaunchKernelGGL(k_gen_logw_update, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, (long)n, log_q, log_p, c,
                        next, log_w);
+    return check_launch();
+}
+
+int fabhip_log_w_first(const float* log_q, const float* log_p, int64_t n, fabhip_anneal next, float* log_w,
+                       fabhip_stream_t stream) {
+    if (!log_q || !log_p || !log_w || n < 0) return FABHIP_EINVAL;
+    if (n == 0) return FABHIP_OK;
+    hipLaunchKernelGGL(k_gen_logw_first, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, (long)n, log_q, log_p, next, log_w);
     return check_launch();
 }
 

@@ -119,6 +119,19 @@ struct SmcK {
 };
 int smc_decide(const SmcK& a, hipStream_t st);
 
+// The next temperature of an adaptive annealing schedule (include/fabhip.h: fabhip_next_beta; reduce_resample.hip: k_next_beta),
+// one workgroup: the largest step delta in (0, 1 - beta] - by K bisections - at which the ESS of the fixed-point weights of
+// log_w + delta s (log_p - log_q) over the first n0 rows is still rho times the ESS of log_w.
+struct NextBetaK {
+    const float *log_w, *log_q, *log_p;    // [B]
+    const int* n_ptr;                  // rows in use (device; null: B)
+    long B;
+    double beta, s, rho;               // s: d pi_beta / d beta = s (log_p - log_q); 1 when the AIS target is p, else alpha
+    int iters;                         // K
+    double* out;                       // [4]: beta_next, ess0, ess at the choice, evaluations + 2^16 floor
+};
+int next_beta(const NextBetaK& a, hipStream_t st);
+
 // 4-chain tiles (flow_r4.h) pay when 16-chain tiles cannot fill the chip: up to 288 workgroups of 4 chains (B <= 1152); off in fast
 // mode (no bf16 variant).  FABHIP_OPT_TILE_SHAPE = 16 / 4 forces the choice (tests exercise both).  D <= 32 and hidden width <= 320
 // only (the other instantiations spill registers and are not compiled).  Used by the transitions, the chain initialisation and

@@ -1906,6 +1906,142 @@ int smc_decide(const SmcK& a, hipStream_t st) {
     return check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Adaptive annealing schedule: the next temperature by ESS-decay bisection (launch.h: NextBetaK; include/fabhip.h:
+// fabhip_next_beta states the definition, tests/adaptive_spec.py restates it).  One workgroup runs the 2 + K evaluations of
+//     ess_of(v) = (sum W)^2 / (n0 sum W^2),   W = fixed-point weights of v[:n0]   (the integer sums of k_smc_decide)
+// on candidates v_i = float32(lw_i + float32((delta s) d_i)).  An evaluation is two block reductions - the largest finite
+// candidate, then (sum W, sum W^2) - each 6 wave shuffles and ONE 16-entry LDS stage; every 16-lane group adds the 16 wave
+// partials itself (4 more shuffles) and every thread evaluates the float64 expression and the comparison (integer sums: the
+// same bits in every thread), so the bisection's branch is uniform without a third barrier.  n0 <= NB_REG x 1024: lw and d stay in registers across the
+// evaluations; above, every evaluation re-reads log_w / log_q / log_p (rows at and beyond n0 are never read).
+// ------------------------------------------------------------------------------------------------
+constexpr int NB_THREADS = 1024, NB_WAVES = NB_THREADS / 64, NB_REG = 8;
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off) {
+    const unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// float32(lw + float32((delta s) d)): one float64 product chain, one rounding to float32, one float32 add; ds < 0: lw itself
+__device__ __forceinline__ float nb_cand(float lw, float d, double ds) {
+    return ds < 0.0 ? lw : lw + (float)(ds * (double)d);
+}
+
+template <bool REG>
+__device__ __forceinline__ double nb_ess(const NextBetaK& a, long n0, const float (&lw_r)[NB_REG], const float (&d_r)[NB_REG],
+                                         double ds, float* sh_max, unsigned long long* sh_sum) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // 1. the largest finite candidate (0 when there is none: fixed_point_weights)
+    float mx = -INFINITY;
+    if (REG) {
+#pragma unroll
+        for (int k = 0; k < NB_REG; ++k) {
+            const float v = nb_cand(lw_r[k], d_r[k], ds);          // (slots at and beyond n0 hold NaN)
+            if (isfinite(v)) mx = fmaxf(mx, v);
+        }
+    } else {
+        for (long i = tid; i < n0; i += NB_THREADS) {
+            const float v = nb_cand(a.log_w[i], a.log_p[i] - a.log_q[i], ds);
+            if (isfinite(v)) mx = fmaxf(mx, v);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (lane == 0) sh_max[w] = mx;
+    __syncthreads();
+    // (the 16 wave partials: one entry per lane of a 16-lane group and four more shuffles - a sixteenth of the LDS reads that
+    //  every thread looping over the 16 entries costs, and the LDS pipe is what this kernel waits for)
+    mx = sh_max[lane & (NB_WAVES - 1)];
+    for (int off = NB_WAVES / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (mx == -INFINITY) mx = 0.f;
+    // 2. sum W in 64 bits, sum W^2 in 128
+    unsigned long long s1 = 0ull, lo = 0ull, hi = 0ull;
+    auto add = [&](float v) {
+        const unsigned long long q = fixed_weight(v, mx);
+        const unsigned long long ql = q * q;
+        s1 += q;
+        lo += ql;
+        hi += __umul64hi(q, q) + (lo < ql ? 1ull : 0ull);
+    };
+    if (REG) {
+#pragma unroll
+        for (int k = 0; k < NB_REG; ++k) add(nb_cand(lw_r[k], d_r[k], ds));
+    } else {
+        for (long i = tid; i < n0; i += NB_THREADS) add(nb_cand(a.log_w[i], a.log_p[i] - a.log_q[i], ds));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o1 = shfl_xor_u64(s1, off), ol = shfl_xor_u64(lo, off), oh = shfl_xor_u64(hi, off);
+        s1 += o1;
+        lo += ol;
+        hi += oh + (lo < ol ? 1ull : 0ull);
+    }
+    if (lane == 0) { sh_sum[3 * w] = s1; sh_sum[3 * w + 1] = lo; sh_sum[3 * w + 2] = hi; }
+    __syncthreads();      // (sh_max is rewritten only behind this barrier, sh_sum only behind the next evaluation's first one)
+    s1 = sh_sum[3 * (lane & (NB_WAVES - 1))]; lo = sh_sum[3 * (lane & (NB_WAVES - 1)) + 1]; hi = sh_sum[3 * (lane & (NB_WAVES - 1)) + 2];
+    for (int off = NB_WAVES / 2; off > 0; off >>= 1) {
+        const unsigned long long o1 = shfl_xor_u64(s1, off), ol = shfl_xor_u64(lo, off), oh = shfl_xor_u64(hi, off);
+        s1 += o1;
+        lo += ol;
+        hi += oh + (lo < ol ? 1ull : 0ull);
+    }
+    // 3. the float64 expression of the SMC decision (tests/smc_spec.py: decide, step 2)
+    if (s1 == 0ull) return 0.0;
+    const double S1 = (double)s1;
+    const double S2 = (double)hi * 18446744073709551616.0 + (double)lo;
+    return (S1 * S1) / ((double)n0 * S2);
+}
+
+template <bool REG>
+__global__ __launch_bounds__(NB_THREADS) void k_next_beta(NextBetaK a) {
+    __shared__ float sh_max[NB_WAVES];
+    __shared__ unsigned long long sh_sum[3 * NB_WAVES];
+    const int tid = threadIdx.x;
+    long n0 = a.n_ptr ? (long)*a.n_ptr : a.B;
+    n0 = n0 < 0 ? 0 : (n0 > a.B ? a.B : n0);
+    float lw_r[NB_REG], d_r[NB_REG];
+#pragma unroll
+    for (int k = 0; k < NB_REG; ++k) {
+        const long i = (long)k * NB_THREADS + tid;
+        const bool in = REG && i < n0;
+        lw_r[k] = in ? a.log_w[i] : __builtin_nanf("");
+        d_r[k] = in ? a.log_p[i] - a.log_q[i] : 0.f;
+    }
+    int evals = 1, floor_taken = 0;
+    const double ess0 = nb_ess<REG>(a, n0, lw_r, d_r, -1.0, sh_max, sh_sum);
+    const double thr = a.rho * ess0, room = 1.0 - a.beta;
+    double beta_next = 1.0, ess_at = ess0;
+    if (room > 0.0) {
+        ess_at = nb_ess<REG>(a, n0, lw_r, d_r, room * a.s, sh_max, sh_sum);
+        evals = 2;
+        if (!(ess_at >= thr)) {
+            double lo = 0.0, hi = room, ess_lo = ess0, ess_hi = ess_at;
+            for (int it = 0; it < a.iters; ++it) {
+                const double mid = 0.5 * (lo + hi);
+                const double e = nb_ess<REG>(a, n0, lw_r, d_r, mid * a.s, sh_max, sh_sum);
+                if (e >= thr) { lo = mid; ess_lo = e; } else { hi = mid; ess_hi = e; }
+            }
+            evals += a.iters;
+            floor_taken = lo > 0.0 ? 0 : 1;                 // every midpoint failed: room / 2^K, so that every step moves
+            const double delta = floor_taken ? hi : lo;
+            ess_at = floor_taken ? ess_hi : ess_lo;
+            beta_next = fmin(a.beta + delta, 1.0);
+        }
+    }
+    if (tid == 0) {
+        a.out[0] = beta_next; a.out[1] = ess0; a.out[2] = ess_at; a.out[3] = (double)(evals + 65536 * floor_taken);
+    }
+}
+
+int next_beta(const NextBetaK& a, hipStream_t st) {
+    if (!a.log_w || !a.log_q || !a.log_p || !a.out || a.B < 1 || a.B > 0x7fffffffL) return FABHIP_EINVAL;
+    if (!(a.beta >= 0.0 && a.beta <= 1.0) || !(a.rho > 0.0 && a.rho < 1.0) || !(a.s == a.s) || a.iters < 1 || a.iters > 60)
+        return FABHIP_EINVAL;
+    // (the row count lives on the device: the capacity decides - B <= 8192 covers every n0 the register variant can meet)
+    if (a.B <= (long)NB_REG * NB_THREADS) hipLaunchKernelGGL(k_next_beta<true>, dim3(1), dim3(NB_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_next_beta<false>, dim3(1), dim3(NB_THREADS), 0, st, a);
+    return check_launch();
+}
+
 int tail_small(const TailArgs& a, int* dest, hipStream_t st) {
     if (a.B > (long)TAIL_MAX_BLOCKS * ESS_THREADS * 4 || a.B < 1) return FABHIP_ENOTSUP;
     const int nb = grid_for(a.B, ESS_THREADS * 4, ESS_MAX_BLOCKS);          // fabhip_ess_logz's grid for the same row capacity
@@ -2204,6 +2340,14 @@ int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, doubl
     k.cdf = (unsigned long long*)workspace; k.anc = ancestors; k.flag = resampled; k.lw_common = log_w_common;
     k.resampled_out = nullptr; k.ess_out = ess; k.anc_out = nullptr; k.lw_pre_out = log_w_pre; k.method = method;
     return smc_decide(k, (hipStream_t)stream);
+}
+
+int fabhip_next_beta(const float* log_w, const float* log_q, const float* log_p, int64_t B, const int32_t* n_ptr, double beta,
+                     double alpha, int32_t p_target, double rho, int32_t iters, double* out4, fabhip_stream_t stream) {
+    NextBetaK k;
+    k.log_w = log_w; k.log_q = log_q; k.log_p = log_p; k.n_ptr = n_ptr; k.B = (long)B; k.beta = beta;
+    k.s = p_target ? 1.0 : alpha; k.rho = rho; k.iters = iters; k.out = out4;
+    return next_beta(k, (hipStream_t)stream);
 }
 
 int fabhip_gather_rows(const float* src, const int64_t* idx, float* dst, int64_t n_out, int64_t row_len,

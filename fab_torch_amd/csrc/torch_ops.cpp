@@ -836,6 +836,15 @@ void log_w_update(const Tensor& log_q, const Tensor& log_p, double beta, double 
         "log_w_update");
 }
 
+// The first weight of a chain whose initialisation ran at beta = 0 (fabhip_log_w_first; adaptive schedules).
+void log_w_first(const Tensor& log_q, const Tensor& log_p, double beta_next, double alpha, bool p_target, Tensor log_w) {
+    c10::DeviceGuard g(log_q.device());
+    need_n(log_p, log_q.numel(), log_q, "log_p"); need_n(log_w, log_q.numel(), log_q, "log_w");
+    chk(fabhip_log_w_first(fp(log_q, "log_q"), fp(log_p, "log_p"), log_q.numel(), coefs(beta_next, alpha, p_target),
+                           fpm(log_w, "log_w"), stream_of(log_q)),
+        "log_w_first");
+}
+
 Tensor metropolis_generic_propose(const Tensor& x, const Tensor& noise_x, const Tensor& scale) {
     c10::DeviceGuard g(x.device());
     Tensor xn = at::empty_like(x);
@@ -1228,6 +1237,28 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smc_decide(const Tensor& log_w, doubl
                           (int32_t)method, stream_of(log_w)),
         "smc_decide");
     return {anc.to(at::kLong), flag, ess, common};
+}
+
+// The next temperature of an adaptive schedule (fabhip_next_beta): float64 [4] = beta_next, ess0, ESS at the choice,
+// evaluations + 2^16 floor.  The output is the op's own tensor and nothing else is written: a call made in pieces keeps the
+// state FABHIP_AIS_INIT left in its workspace.
+Tensor next_beta(const Tensor& log_w, const Tensor& log_q, const Tensor& log_p, const optional<Tensor>& n_valid, double beta,
+                 double alpha, bool p_target, double rho, int64_t iters) {
+    c10::DeviceGuard g(log_w.device());
+    const int64_t n = log_w.numel();
+    TORCH_CHECK(n >= 1, "fabhip: next_beta needs at least one chain");
+    need_n(log_q, n, log_w, "log_q"); need_n(log_p, n, log_w, "log_p");
+    const int32_t* np = nullptr;
+    if (n_valid.has_value()) {
+        need(*n_valid, at::kInt, "n_valid");
+        TORCH_CHECK(n_valid->numel() >= 1 && n_valid->device() == log_w.device(), "fabhip: n_valid must be int32 on log_w's device");
+        np = n_valid->data_ptr<int32_t>();
+    }
+    Tensor out = at::empty({4}, log_w.options().dtype(at::kDouble));
+    chk(fabhip_next_beta(fp(log_w, "log_w"), fp(log_q, "log_q"), fp(log_p, "log_p"), n, np, beta, alpha, p_target ? 1 : 0, rho,
+                         (int32_t)iters, out.data_ptr<double>(), stream_of(log_w)),
+        "next_beta");
+    return out;
 }
 
 // SMC mode over sharded chains (fabhip_smc_shard_pack / fabhip_smc_shard_resample; fab_torch_amd/parallel.py steps the loop).
@@ -1635,6 +1666,9 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor(q!)? base_log_w, int precision, float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
           "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre, int method=0) -> ()");
     m.def("smc_decide(Tensor log_w, float tau, Tensor u, int method=0) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("next_beta(Tensor log_w, Tensor log_q, Tensor log_p, Tensor? n_valid, float beta, float alpha, bool p_target, "
+          "float rho, int iters=24) -> Tensor");
+    m.def("log_w_first(Tensor log_q, Tensor log_p, float beta_next, float alpha, bool p_target, Tensor(a!) log_w) -> ()");
     m.def("smc_shard_pack(Tensor x, Tensor log_q, Tensor log_p, Tensor? grad_log_q, Tensor? grad_log_p, Tensor log_w, "
           "Tensor n_valid) -> Tensor");
     m.def("smc_shard_resample(Tensor gathered, int world, int rank, float tau, Tensor u, Tensor(a!) x, Tensor(b!) log_q, "
@@ -1724,6 +1758,8 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("ais_run_mix", ais_run_mix);
     m.impl("defensive_log_prob", defensive_log_prob);
     m.impl("smc_decide", smc_decide);
+    m.impl("next_beta", next_beta);
+    m.impl("log_w_first", log_w_first);
     m.impl("smc_shard_pack", smc_shard_pack);
     m.impl("smc_shard_resample", smc_shard_resample);
     m.impl("ais_sharded_tuned", ais_sharded_tuned);

@@ -127,6 +127,16 @@ def refuse_resample_method(who: str, sampler):
                           "resample_method='systematic' on the sampler")
 
 
+def refuse_adaptive(who: str, sampler):
+    """An adaptive schedule chooses every temperature from the weights of ALL chains of a call: the sharded samplers, whose
+    ranks keep their chains to themselves, refuse it (a schedule of the caller's - the `last_betas` of a single-device run, for
+    instance - works on every route)."""
+    if getattr(sampler, "adaptive", False):
+        from ._ops import FabhipError
+        raise FabhipError(f"{who}: distribution_spacing_type='adaptive' is not available for sharded chains; set "
+                          "distribution_spacing_type to 'linear', 'geometric' or a schedule of your own on the sampler")
+
+
 def refuse_mixture(who: str, sampler):
     """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_run_mix has no `partials` form and
     the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
@@ -156,6 +166,7 @@ class ShardedAIS:
         sizes = shard_sizes(total_batch, world)
         refuse_resampling("ShardedAIS", getattr(getattr(self.local_sampler, "__self__", None), "resample_threshold", None))
         refuse_mixture("ShardedAIS", getattr(self.local_sampler, "__self__", None))
+        refuse_adaptive("ShardedAIS", getattr(self.local_sampler, "__self__", None))
         x, log_w, log_q = self.local_sampler(sizes[rank])
         if self.sync_step_size and self.step_state is not None and world > 1:
             # ONE tiny all-reduce for all step-size tensors (epsilons [M, n_outer] + common_epsilon [1]: latency-bound)
@@ -433,6 +444,7 @@ class ShardedAnnealedImportanceSampler:
         be = self.backend
         tau = getattr(getattr(be, "ais", None), "resample_threshold", None)
         smc_on = self.resample_across_ranks and tau is not None
+        refuse_adaptive("ShardedAnnealedImportanceSampler", getattr(be, "ais", None))
         if not self.resample_across_ranks:
             refuse_resampling("ShardedAnnealedImportanceSampler", tau)
         else:

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 222
+#define FABHIP_ABI_VERSION 223
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -526,6 +526,12 @@ int fabhip_anneal_log_prob(const float* log_q, const float* log_p, int64_t n, fa
 /* log_w += pi_next(point) - pi_c(point)  (ais.py:93-100) */
 int fabhip_log_w_update(const float* log_q, const float* log_p, int64_t n, fabhip_anneal c, fabhip_anneal next,
                         float* log_w, fabhip_stream_t stream);
+/* The first weight of a chain whose FABHIP_AIS_INIT ran with betas[1] = 0 (adaptive schedules, fabhip_next_beta): there
+ * log_w = log_q - log_q0 exactly (two float32 values of one density, Sterbenz), so this writes
+ *     log_w = pi_next(point) - (log_q - log_w)  =  pi_next(point) - log_q0
+ * - the bits FABHIP_AIS_INIT writes when it is given betas[1] = beta_1 itself. */
+int fabhip_log_w_first(const float* log_q, const float* log_p, int64_t n, fabhip_anneal next, float* log_w,
+                       fabhip_stream_t stream);
 int fabhip_metropolis_generic_propose(const float* x, const float* noise_x, const float* scale_ptr, int64_t B, int32_t dim,
                                       float* x_new, fabhip_stream_t stream);
 int fabhip_metropolis_generic_accept(const float* x_new, const float* new_log_q, const float* new_log_p,
@@ -679,6 +685,25 @@ size_t fabhip_smc_workspace_bytes(int64_t B);
 int fabhip_smc_decide(const float* log_w, int64_t B, const int32_t* n_ptr, double tau, const double* u, int32_t* ancestors,
                       int32_t* resampled, float* ess, float* log_w_common, float* log_w_pre, void* workspace,
                       size_t workspace_bytes, int32_t method, fabhip_stream_t stream);
+
+/* The next temperature of an ADAPTIVE annealing schedule by ESS-decay bisection (definition: tests/adaptive_spec.py; one
+ * workgroup, one launch).  With n0 = *n_ptr live rows (NULL: B; rows at and beyond n0 are never read), float32 throughout
+ * unless stated:
+ *     lw = log_w[:n0];  d = log_p - log_q (one float32 subtract);  s = 1 if p_target else alpha (float64)
+ *     ess_of(v): W = the resampler's fixed-point weights of v (exp_spec, floor(p 2^36); a NaN / infinite entry weighs 0),
+ *                S1i = sum W, S2i = sum W^2 as exact integers; S1i == 0: 0, else the float64 expression of the SMC decision,
+ *                (S1 S1) / (float64(n0) S2)
+ *     cand(delta) = float32(lw + float32((float64(delta) s) float64(d)))
+ *     ess0 = ess_of(lw);  thr = rho ess0;  room = 1 - beta                                      (float64)
+ *     room > 0 fails: 1;  ess_of(cand(room)) >= thr: 1
+ *     else lo, hi = 0, room; `iters` (K) times: mid = (lo + hi) / 2; ess_of(cand(mid)) >= thr ? lo = mid : hi = mid
+ *          delta = lo > 0 ? lo : hi  (the floor room / 2^K, so that every step moves);  min(beta + delta, 1)
+ * out4 (device, float64): beta_next, ess0, the ESS at the chosen step (at the floor: of the floor step, below thr; without a
+ * bisection: of the last candidate evaluated), evaluations + 2^16 (1 if the floor was taken).  The criterion is relative, so it
+ * reads the same after a resampling step has made the weights equal.  ESS need not be monotone in delta: the bisection is the
+ * definition.  beta in [0, 1], rho in (0, 1), 1 <= iters <= 60, else FABHIP_EINVAL.  No workspace. */
+int fabhip_next_beta(const float* log_w, const float* log_q, const float* log_p, int64_t B, const int32_t* n_ptr, double beta,
+                     double alpha, int32_t p_target, double rho, int32_t iters, double* out4, fabhip_stream_t stream);
 
 /* SMC mode over SHARDED chains (fab_torch_amd/parallel.py: resample_across_ranks; definition: tests/smc_shard_spec.py).
  * R ranks hold b rows each, the first n_r = n_valid[0] of them live; the global live order is the ranks' live rows in rank
