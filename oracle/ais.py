@@ -115,6 +115,20 @@ class HMC:
 
     uses_grad_info = True
 
+    # the three places the mass vector enters (hmc.py:134, :142, :126-127), one line each: tests/hmc_mass_cases.py
+    # overrides them one at a time to state what a wrong convention would compute
+    def _momentum(self, noise):
+        return noise * self.mass_vector
+
+    def _position(self, x, eps, p):
+        return x + eps / self.mass_vector * p
+
+    def _kinetic(self, p):
+        return torch.sum(p ** 2 / self.mass_vector, -1) / 2
+
+    def _outer_step_done(self, proposal):
+        """after every outer step (last_accept / last_margin / last_p_accept are this step's): tests record what they need"""
+
     def _U(self, pt, beta):
         return -intermediate_log_prob(pt, beta, self.alpha, self.p_target)
 
@@ -128,17 +142,17 @@ class HMC:
         current = point
         for n in range(self.n_outer):
             eps = self.epsilons[i - 1, n] + self.common_epsilon
-            p = noise_p[n, : point.x.shape[0]] * self.mass_vector
+            p = self._momentum(noise_p[n, : point.x.shape[0]])
             current_p = p
             grad_u = self._grad_U(point, beta)
             for _ in range(self.L):
                 p = p - eps * grad_u / 2
-                x = point.x + eps / self.mass_vector * p
+                x = self._position(point.x, eps, p)
                 point = create_point(x, self.log_q_fn, self.log_p_fn, with_grad=True)
                 grad_u = self._grad_U(point, beta)
                 p = p - eps * grad_u / 2
-            lp_cur = -self._U(current, beta) - torch.sum(current_p ** 2 / self.mass_vector, -1) / 2
-            lp_prop = -self._U(point, beta) - torch.sum(p ** 2 / self.mass_vector, -1) / 2
+            lp_cur = -self._U(current, beta) - self._kinetic(current_p)
+            lp_prop = -self._U(point, beta) - self._kinetic(p)
             log_acc = lp_prop - lp_cur
             # distance of the accept decision from its threshold (tests: a chain may only differ from this oracle
             # through a decision that sits within rounding of the threshold)
@@ -151,6 +165,7 @@ class HMC:
             log_p_accept_mean = torch.logsumexp(log_acc, -1) - torch.log(torch.tensor(log_acc.shape[0]))
             current[accept] = point[accept]
             self.last_accept, self.last_p_accept = accept, torch.exp(log_p_accept_mean)
+            self._outer_step_done(point)
             if not self.eval_mode:
                 if log_p_accept_mean > torch.log(torch.tensor(self.target_p_accept)):
                     self.epsilons[i - 1, n] = self.epsilons[i - 1, n] * 1.05
