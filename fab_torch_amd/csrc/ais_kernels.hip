@@ -1133,7 +1133,7 @@ __global__ void k_compact_copyback(CompactK a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// SMC mode: the gather of the point with the ancestors of k_smc_decide (reduce_resample.hip), through the compaction's staging
+// SMC mode: the gather of the point with the ancestors of k_smc_decide (weight_decisions.hip), through the compaction's staging
 // buffer and back.  Both kernels are always launched and read the device flag: the host's launch sequence is fixed.
 // ------------------------------------------------------------------------------------------------
 struct SmcGatherK {

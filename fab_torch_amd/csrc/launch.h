@@ -77,7 +77,7 @@ struct SplineLeap {
 int spline_log_prob_leap(const fabhip_spline_flow* flow, const SplineLeap& lp, float* log_q, float* grad_x, int64_t B,
                          void* workspace, size_t workspace_bytes, hipStream_t st);
 
-// The tail of a chain phase in one launch for small batches (reduce_resample.hip: k_tail_small): compaction of the rows with
+// The tail of a chain phase in one launch for small batches (reduce_kernels.hip: k_tail_small): compaction of the rows with
 // finite log_p / log_q, optionally diff = log_p - log_q over all B rows, ESS / log Z over the survivors (of diff, or of log_w).
 // FABHIP_ENOTSUP above 2048 rows (the caller then runs the separate kernels: the same results, bit for bit).
 struct TailArgs {
@@ -97,7 +97,7 @@ struct TailArgs {
 };
 int tail_small(const TailArgs& a, int* dest, hipStream_t st);
 
-// The decision of the SMC mode (include/fabhip.h: fabhip_smc_args; reduce_resample.hip: k_smc_decide), one workgroup: fixed-point
+// The decision of the SMC mode (include/fabhip.h: fabhip_smc_args; weight_decisions.hip: k_smc_decide), one workgroup: fixed-point
 // weights W of log_w[:n0] (the resampler's own exp_spec / fixed_weight), their integer CDF, ESS = (sum W)^2 / (n0 sum W^2) from
 // exact integer sums, the device flag `ESS < tau`, the common log-weight after resampling and the systematic (or stratified:
 // `method`) ancestors of the first n0 rows (identity where the flag is off, and for the rows beyond n0).
@@ -119,7 +119,7 @@ struct SmcK {
 };
 int smc_decide(const SmcK& a, hipStream_t st);
 
-// The next temperature of an adaptive annealing schedule (include/fabhip.h: fabhip_next_beta; reduce_resample.hip: k_next_beta),
+// The next temperature of an adaptive annealing schedule (include/fabhip.h: fabhip_next_beta; weight_decisions.hip: k_next_beta),
 // one workgroup: the largest step delta in (0, 1 - beta] - by K bisections - at which the ESS of the fixed-point weights of
 // log_w + delta s (log_p - log_q) over the first n0 rows is still rho times the ESS of log_w.
 struct NextBetaK {

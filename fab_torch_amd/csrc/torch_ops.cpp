@@ -1478,32 +1478,34 @@ Tensor resample_systematic(const Tensor& log_w, double u0, int64_t n_samples) {
     return idx;
 }
 
-// seeded streaming multinomial: the 64 bits of `seed` are the C ABI's uint64 seed (order: FABHIP_ORDER_*)
-// Seeded stratified resampling indices (fabhip_resample_stratified): int64 [n_samples], non-decreasing for order = 0.
-Tensor resample_stratified(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
+// The seeded resamplers (one C signature): int64 [n_samples] indices; the 64 bits of `seed` are the C ABI's uint64 seed
+// (order: FABHIP_ORDER_*)
+using SeededSizeFn = size_t (*)(int64_t, int64_t);
+using SeededFn = int (*)(const float*, int64_t, uint64_t, int64_t, int32_t, int64_t*, void*, size_t, fabhip_stream_t);
+static Tensor resample_seeded(SeededSizeFn size_fn, SeededFn fn, const char* name, const Tensor& log_w, int64_t seed,
+                              int64_t n_samples, int64_t order) {
     c10::DeviceGuard g(log_w.device());
     const int64_t n = log_w.numel();
-    TORCH_CHECK(n_samples >= 1, "fabhip::resample_stratified: n_samples must be >= 1");
+    TORCH_CHECK(n_samples >= 1, "fabhip::", name, ": n_samples must be >= 1");
     Tensor idx = at::empty({n_samples}, log_w.options().dtype(at::kLong));
-    const size_t nb = fabhip_resample_stratified_workspace_bytes(n, n_samples);
+    const size_t nb = size_fn(n, n_samples);
     Tensor ws = scratch(nb, log_w);
-    chk(fabhip_resample_stratified(fp(log_w, "log_w"), n, (uint64_t)seed, n_samples, (int32_t)order, idx.data_ptr<int64_t>(),
-                                   aligned(ws), nb, stream_of(log_w)),
-        "resample_stratified");
+    chk(fn(fp(log_w, "log_w"), n, (uint64_t)seed, n_samples, (int32_t)order, idx.data_ptr<int64_t>(), aligned(ws), nb,
+           stream_of(log_w)),
+        name);
     return idx;
 }
 
+// Seeded stratified resampling indices (fabhip_resample_stratified): non-decreasing for order = 0.
+Tensor resample_stratified(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
+    return resample_seeded(fabhip_resample_stratified_workspace_bytes, fabhip_resample_stratified, "resample_stratified", log_w,
+                           seed, n_samples, order);
+}
+
+// seeded streaming multinomial (fabhip_resample_multinomial_stream)
 Tensor resample_multinomial_stream(const Tensor& log_w, int64_t seed, int64_t n_samples, int64_t order) {
-    c10::DeviceGuard g(log_w.device());
-    const int64_t n = log_w.numel();
-    TORCH_CHECK(n_samples >= 1, "fabhip::resample_multinomial_stream: n_samples must be >= 1");
-    Tensor idx = at::empty({n_samples}, log_w.options().dtype(at::kLong));
-    const size_t nb = fabhip_resample_stream_workspace_bytes(n, n_samples);
-    Tensor ws = scratch(nb, log_w);
-    chk(fabhip_resample_multinomial_stream(fp(log_w, "log_w"), n, (uint64_t)seed, n_samples, (int32_t)order,
-                                           idx.data_ptr<int64_t>(), aligned(ws), nb, stream_of(log_w)),
-        "resample_multinomial_stream");
-    return idx;
+    return resample_seeded(fabhip_resample_stream_workspace_bytes, fabhip_resample_multinomial_stream,
+                           "resample_multinomial_stream", log_w, seed, n_samples, order);
 }
 
 Tensor multinomial_torch(const Tensor& probs, const Tensor& u) {

@@ -1,6 +1,6 @@
-"""Named inputs of the fixed-point resamplers (fabhip_resample_multinomial / fabhip_resample_systematic, csrc/reduce_resample.hip)
-shared by test_resample_fixed_cases.py (CPU: every case reaches the device branch it is listed for, judged from the oracle's
-output alone) and test_gpu_resample_fixed.py (GPU: bit-exact against oracle/numerical.py).  No test functions here.
+"""Named inputs of the fixed-point resamplers (fabhip_resample_multinomial, csrc/resample_scan.hip; fabhip_resample_systematic,
+csrc/resample_emit.hip and, for its scan + search path, resample_scan.hip) shared by test_resample_fixed_cases.py (CPU: every
+case reaches the device branch it is listed for, judged from the oracle's output alone) and test_gpu_resample_fixed.py (GPU: bit-exact against oracle/numerical.py).  No test functions here.
 
 A case is (name, float32 log_w from a seeded np.random.default_rng, the n_samples to draw, the u0 to draw them with).  The
 constants below restate the kernel constants that decide which branch a wave takes; a change on either side shows up in the CPU
@@ -12,7 +12,7 @@ import numpy as np
 
 from oracle import numerical as onum
 
-# ---- kernel constants that decide a branch (csrc/reduce_resample.hip) ----
+# ---- kernel constants that decide a branch (EM_*: csrc/resample_emit.hip; SCAN_* / SYS_*: csrc/resample_scan.hip) ----
 EM_WAVE_ITEMS = 1024        # constexpr int EM_WAVE_ITEMS: weights per wave of k_emit_systematic
 EM_NW = 4                   # constexpr int EM_NW: waves per workgroup (EM_BLOCK = EM_WAVE_ITEMS * EM_NW)
 EM_WIN = 1536               # constexpr int EM_WIN: strata per marker window

@@ -32,6 +32,14 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"workspace" in lib.fabhip_strerror(-4)
 
 
+def test_build_sources_are_exactly_the_hip_files_of_csrc():
+    """A unit that was added, renamed or deleted without its entry in _build.SOURCES fails here, not at link time on a GPU box."""
+    from fab_torch_amd import _build
+    present = sorted(f for f in os.listdir(_build.CSRC) if f.endswith(".hip"))
+    assert len(set(_build.SOURCES)) == len(_build.SOURCES), "duplicate entry in _build.SOURCES"
+    assert sorted(_build.SOURCES) == present
+
+
 def test_abi_revision_and_developer_switches_without_gpu():
     """The ABI revision of the header, of both bindings and of the library agree; every developer switch of the header exists in
     the library with the default the header documents (the round-4 paths - one-launch phase tails, the in-kernel step-size rule,

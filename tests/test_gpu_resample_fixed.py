@@ -1,5 +1,6 @@
 """GPU tests of the fixed-point resamplers behind `resample` (fabhip_fixed_cdf, fabhip_resample_multinomial,
-fabhip_resample_systematic on both of its paths, fabhip_gather_rows; csrc/reduce_resample.hip) against oracle/numerical.py on the
+fabhip_resample_systematic on both of its paths, fabhip_gather_rows; csrc/resample_scan.hip, resample_emit.hip and
+reduce_kernels.hip) against oracle/numerical.py on the
 cases of tests/resample_fixed_cases.py: sizes around every lane-row / node / tile / workgroup boundary, more and fewer draws than
 weights, degenerate weights (test_resample_fixed_cases.py holds each case to the branch it is listed for).  Integer work with an
 exact statement: every comparison is bit for bit.

@@ -119,7 +119,7 @@ def test_limits_are_stated():
         assert spec.MAX_SAMPLES * S <= total << F < 1 << 62 and S >= 1 << 30
 
 
-# ---- the estimates of the kernel (csrc/reduce_resample.hip: stratified_rel / stratified_rel_small) ------------------------
+# ---- the estimates of the kernel (csrc/resample_emit.hip: stratified_rel / stratified_rel_small) --------------------------
 def _wave_estimates(C, ns):
     """Per wave tile: (T bound, |estimate - exact| of the fp32 quotient relative to the wave's stratum q0, the same for the
     float64 quotient) - the exact step that follows corrects a miss of ONE stratum, not more."""

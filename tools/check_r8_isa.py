@@ -10,7 +10,8 @@ sys.path.insert(0, ROOT)
 from fab_torch_amd import _isa_check as chk          # noqa: E402
 
 BUILD = os.path.join(ROOT, "fab_torch_amd", "build")
-DEVICE_OBJECTS = ("flow_kernels", "ais_kernels", "spline_kernels", "train_kernels", "reduce_resample", "generic_kernels", "topk")
+DEVICE_OBJECTS = ("flow_kernels", "ais_kernels", "spline_kernels", "train_kernels", "reduce_kernels", "resample_scan",
+                  "resample_emit", "weight_decisions", "generic_kernels", "topk")
 
 
 def main():
