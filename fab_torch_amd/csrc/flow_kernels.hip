@@ -362,9 +362,7 @@ static int launch_log_prob(const FlowDims& f, const float* packed, const float* 
         const FlowLds l = make_flow_lds(f, true);
         const size_t bytes = (size_t)l.total * 4;
         if (f.fast) {
-            FAB_TRY(set_max_lds((const void*)k_flow_log_prob_fast<NTWM>, bytes));
-            hipLaunchKernelGGL((k_flow_log_prob_fast<NTWM>), grid, block, bytes, st, f, l, packed, x, log_q, grad, B);
-            return check_launch();
+            return launch_lds(k_flow_log_prob_fast<NTWM>, grid, block, bytes, st, f, l, packed, x, log_q, grad, B);
         }
         FAB_TRY(set_max_lds((const void*)k_flow_log_prob<NTWM, true>, bytes));
         hipLaunchKernelGGL((k_flow_log_prob<NTWM, true>), grid, block, bytes, st, f, l, packed, x, log_q, grad, B);
@@ -741,9 +739,7 @@ static int launch_sample(const FlowDims& f, const float* packed, const float* ep
     const dim3 grid((unsigned)ceil_div((int)B, ROWS)), block(NTHREADS);
     const FlowLds l = make_flow_lds(f, false);
     const size_t bytes = (size_t)l.total * 4;
-    FAB_TRY(set_max_lds((const void*)k_flow_sample<NTWM>, bytes));
-    hipLaunchKernelGGL((k_flow_sample<NTWM>), grid, block, bytes, st, f, l, packed, eps, x, log_q, B);
-    return check_launch();
+    return launch_lds(k_flow_sample<NTWM>, grid, block, bytes, st, f, l, packed, eps, x, log_q, B);
 }
 
 }  // namespace fab

@@ -257,7 +257,7 @@ static void split_ws(void* ws, long B, int D, float*& XP, float*& P, float*& GU,
     pd = w;
 }
 
-// begin / accept with the row count read on the device (launch.h): the fused spline AIS call (ais_kernels.hip) keeps
+// begin / accept with the row count read on the device (launch.h): the fused spline AIS call (ais_driver.hip) keeps
 // fixed-size buffers after the "chain init" filter, like fabhip_ais_run
 void gen_hmc_state(void* workspace, long B, int dim, float** XP, float** P, float** GU) {
     float *row, *pa, *pd;

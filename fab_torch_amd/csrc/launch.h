@@ -175,6 +175,30 @@ static inline int set_max_lds(const void* fn, size_t bytes) {
     return FABHIP_OK;
 }
 
+// The launch triple of every kernel with dynamic LDS: raise the kernel's LDS limit where needed, launch, report.  The kernel's
+// parameters and the arguments are deduced separately: the arguments convert as at a direct launch (nullptr, const float*).
+template <class... P, class... A>
+static inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, A&&... args) {
+    FAB_TRY(set_max_lds((const void*)kernel, lds_bytes));
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, static_cast<A&&>(args)...);
+    return check_launch();
+}
+
+// workspace layouts: every block rounded up to 256 bytes
+static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Bump {             // bump allocator over a workspace: every block rounded up to `align` bytes
+    char* p;
+    size_t align;
+    template <class T>
+    T* take(size_t count) {
+        T* q = (T*)p;
+        p += (count * sizeof(T) + align - 1) / align * align;
+        return q;
+    }
+};
+// A layout is written once, as a carve function that returns its pointers and `bytes`: carve(nullptr, ...).bytes is the size the
+// matching *_workspace_bytes reports, so the two cannot drift apart.
+
 // compute units of the current device (cached: the tile-shape choices compare the batch with chains-per-workgroup x CUs)
 static inline int cu_count() {
     static const int n = [] {

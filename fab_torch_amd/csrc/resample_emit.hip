@@ -795,18 +795,7 @@ struct EmitWs {           // what the kernels the three resamplers share read an
     long giant_cap, nwt, nbk;
 };
 
-struct Bump {             // bump allocator over a workspace: every block rounded up to `align` bytes
-    char* p;
-    size_t align;
-    template <class T>
-    T* take(size_t count) {
-        T* q = (T*)p;
-        p += (count * sizeof(T) + align - 1) / align * align;
-        return q;
-    }
-};
-
-// The common blocks, out of `b`.  max_part / max_val: where the caller has them already (null: carved here).  giant_min: the
+// The common blocks, out of `b` (launch.h: Bump).  max_part / max_val: where the caller has them already (null: carved here).  giant_min: the
 // shortest run that is published - at most ns / giant_min + 1 can exist.  room: the 8-byte words the blocks may take in all
 // (< 0: no limit): what the fixed blocks, nwt + 2 nbk + 5 words, leave of it bounds the list of runs, 3 words each.
 static EmitWs carve_emit_ws(Bump& b, float* max_part, float* max_val, long n, long ns, long giant_min, long room) {

@@ -1,11 +1,10 @@
 // Host-side pieces the reduction / resampler units share (reduce_kernels.hip, resample_scan.hip, resample_emit.hip,
-// weight_decisions.hip): rounding and grid helpers, and what the scan unit launches on behalf of the emit unit.
+// weight_decisions.hip): the grid helper (al256 and Bump: launch.h), and what the scan unit launches on behalf of the emit unit.
 #pragma once
 #include "launch.h"
 
 namespace fab {
 
-static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int grid_for(long n, int threads, int cap) {
     long b = (n + threads - 1) / threads;
     if (b < 1) b = 1;

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_spline_pack_r8(SplineDims f, SplineSrc 
 // Round 5: the REST of an HMC outer step (hmc.py:129-160) inside the leapfrog launches - `flags` & 1: this launch is the first
 // leapfrog and does k_gen_hmc_begin's work at its top (p0 = noise x mass, grad U of the start point, -U(current) - K(p0));
 // & 2: it is the last one and does k_gen_hmc_accept's (accept / reject, commit, AIS log-weight increment) and k_gen_hmc_adapt's
-// (step-size rule, by the last wave of the launch to finish: the mechanism of ais_kernels.hip's hmc_adapt_last) at its end:
+// (step-size rule, by the last wave of the launch to finish: the mechanism of ais_device.h's hmc_adapt_last) at its end:
 // a transition is L launches instead of L + 3.  Every sum is formed in the order of the kernels it replaces (16 lanes per chain:
 // lane c adds coordinates c, c + 16, ..; xor butterfly 8, 4, 2, 1; 16 chains per block in row order; blocks in order): bit-identical.
 using SplineFoldDev = SplineFold;     // launch.h
@@ -199,7 +199,7 @@ __device__ __forceinline__ float s8_row16_sum_xor(float v) {                   /
     v += __shfl_xor(v, 1);
     return v;
 }
-// k_gen_hmc_adapt's work by the last wave of the launch to finish.  Cross-workgroup ordering as in ais_kernels.hip
+// k_gen_hmc_adapt's work by the last wave of the launch to finish.  Cross-workgroup ordering as in ais_device.h
 // (hmc_store_row_stats / hmc_adapt_last; _isa_check.py pins the lowering): per-chain values written through (sc1) by
 // device-scope relaxed atomic stores, vmcnt(0), ticket; the last ticket's wave reads them past its XCD's L2 (sc1 loads).
 // Every wave of every workgroup calls this once, after its stores.  `scratch`: 2 nblk floats of LDS nobody else touches.

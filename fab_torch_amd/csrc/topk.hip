@@ -315,9 +315,7 @@ int fabhip_topk(const float* keys, int64_t n, int64_t k, int32_t sorted, int64_t
     int np2 = 1;
     while (np2 < k) np2 <<= 1;
     const size_t lds = (size_t)np2 * 8;
-    FAB_TRY(set_max_lds((const void*)k_topk_sort, lds));
-    hipLaunchKernelGGL(k_topk_sort, dim3(1), dim3(1024), lds, st, ws.sel, (long)k, (long long*)idx_out, key_out);
-    return check_launch();
+    return launch_lds(k_topk_sort, dim3(1), dim3(1024), lds, st, ws.sel, (long)k, (long long*)idx_out, key_out);
 }
 
 int fabhip_buffer_add(const float* x, const float* log_w, const float* log_q_old, int64_t n, int32_t dim, int64_t start,

@@ -504,9 +504,7 @@ static int launch_log_prob_tape(const FlowDims& f, const TapeDims& td, const flo
     const dim3 grid((unsigned)ceil_div((int)B, ROWS)), block(NTHREADS);
     const FlowLds l = make_flow_lds(f, true);
     const size_t bytes = (size_t)l.total * 4;
-    FAB_TRY(set_max_lds((const void*)k_flow_log_prob_tape<NTWM>, bytes));
-    hipLaunchKernelGGL((k_flow_log_prob_tape<NTWM>), grid, block, bytes, st, f, l, td, packed, x, log_q, grad, tape, B, rows);
-    return check_launch();
+    return launch_lds(k_flow_log_prob_tape<NTWM>, grid, block, bytes, st, f, l, td, packed, x, log_q, grad, tape, B, rows);
 }
 
 template <int NTWM>
@@ -515,9 +513,7 @@ static int launch_sample_bwd(const FlowDims& f, const TapeDims& td, const float*
     const dim3 grid((unsigned)ceil_div((int)B, ROWS)), block(NTHREADS);
     const FlowLds l = make_flow_lds(f, false);
     const size_t bytes = ((size_t)l.total + ROWS * l.DS + 2 * NTHREADS) * 4;
-    FAB_TRY(set_max_lds((const void*)k_flow_sample_bwd<NTWM>, bytes));
-    hipLaunchKernelGGL((k_flow_sample_bwd<NTWM>), grid, block, bytes, st, f, l, td, packed, x, gx, gl, g_eps, tape, B);
-    return check_launch();
+    return launch_lds(k_flow_sample_bwd<NTWM>, grid, block, bytes, st, f, l, td, packed, x, gx, gl, g_eps, tape, B);
 }
 
 int launch_affine_grads(const FlowDims& f, const TapeDims& td, const GradLayout& gl, const fabhip_flow_params* params,

@@ -9,7 +9,7 @@ namespace fab {
 
 // ------------------------------------------------------------------------------------------------
 // SMC mode of the fused AIS call: the decision in front of a transition (launch.h: SmcK).  A few thousand chains: ONE
-// workgroup reduces, scans and searches; the point is gathered grid-wide afterwards (ais_kernels.hip).  Every sum that decides
+// workgroup reduces, scans and searches; the point is gathered grid-wide afterwards (ais_moves.hip).  Every sum that decides
 // is an integer sum (associative: the same bits for any reduction order): sum W < 2^62 in 64 bits, sum W^2 < 2^98 in 128.
 // ------------------------------------------------------------------------------------------------
 constexpr int SMC_THREADS = 1024;

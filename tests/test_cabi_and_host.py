@@ -222,3 +222,31 @@ def test_spline_flow_module_has_normflows_keys_and_fails_loudly_on_the_cpu():
         hf.log_prob(torch.randn(4, 10))
     with pytest.raises(NotImplementedError):
         fa.CircularCoupledRQSFlow(10, 4, 32, (2, 7), tb, num_bins=4)
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """Every *_workspace_bytes of the AIS units against tests/golden/workspace_bytes.json (host-only functions).  The sizes come
+    out of the carve functions that also hand the drivers their pointers: a block added to one layout shows up here."""
+    import itertools
+    import json
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")) as fh:
+        rec = json.load(fh)
+    i32, i64 = C.c_int32, C.c_int64
+    realnvp = list(itertools.product([1, 15, 16, 17, 1024, 1152, 1153, 2048, 2049, 4096, 32769], [2, 6, 32, 33, 64], [1, 2, 5]))
+    spline = [s + (B,) for s, B in itertools.product([(6, 4, 64), (60, 12, 256)], [16, 1000, 2048])]
+    grids = {"fabhip_hmc_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_metropolis_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_ais_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_ais_smc_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_spline_hmc_workspace_bytes": ([i32, i32, i32, i64], spline),
+             "fabhip_spline_ais_workspace_bytes": ([i32, i32, i32, i64], spline),
+             "fabhip_smc_shard_workspace_bytes": ([i32, i64], list(itertools.product([1, 2, 64], [16, 2048])))}
+    assert sorted(rec) == sorted(grids)
+    for name, (argtypes, cases) in grids.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = C.c_size_t, argtypes
+        want = {tuple(r[:-1]): r[-1] for r in rec[name]}
+        assert sorted(want) == sorted(cases), f"{name}: the fixture does not hold the cases of this test"
+        got = {c: fn(*c) for c in cases}
+        assert got == want, {c: (got[c], want[c]) for c in cases if got[c] != want[c]}

@@ -59,7 +59,7 @@ def test_checker_follows_loop_back_edges():
 
 
 def test_checker_pins_the_lowering_of_the_in_kernel_step_size_rule():
-    """hmc_adapt_last (csrc/ais_kernels.hip) relies on how gfx950 lowers device-scope relaxed atomics: write-through (sc1) stores,
+    """hmc_adapt_last (csrc/ais_device.h) relies on how gfx950 lowers device-scope relaxed atomics: write-through (sc1) stores,
     a ticket drawn behind `s_waitcnt vmcnt(0)`, sc1 loads in the last wave (outside the HIP memory model).  The
     build's ISA check fails when a compiler lowers them differently."""
     name = "_ZN3fab13k_hmc_step_r4ILi5ELb0ELi2EEE"
@@ -78,7 +78,13 @@ def test_checker_pins_the_lowering_of_the_in_kernel_step_size_rule():
     assert any("ticket" in b[1] for b in chk.check_adapt_fold(name, chk.from_lines(late_store)))
 
 
-@pytest.mark.parametrize("stem", ["flow_kernels", "ais_kernels", "spline_kernels", "train_kernels"])
+# the kernels that must still be in the library, on the unit that holds them
+MUST_HOLD = {"ais_tile16": ("k_hmc_stepILi5E",), "ais_tile48": ("k_hmc_step_r4", "k_ais_init_r4", "k_hmc_step_r8", "k_ais_init_r8"),
+             "spline_kernels": ("k_spline_logprob_r8",)}
+
+
+@pytest.mark.parametrize("stem", ["flow_kernels", "ais_tile16", "ais_tile16_metropolis", "ais_tile48", "ais_moves", "spline_kernels",
+                                  "train_kernels"])
 def test_no_instruction_touches_a_register_whose_load_is_in_flight(stem):
     obj = os.path.join(BUILD, stem + ".o")
     if not os.path.exists(obj):
@@ -88,10 +94,7 @@ def test_no_instruction_touches_a_register_whose_load_is_in_flight(stem):
     res = chk.check_object(obj)
     assert res, f"{stem}: no kernels found"
     names = " ".join(res)
-    if stem == "ais_kernels":
-        for k in ("k_hmc_step_r4", "k_ais_init_r4", "k_hmc_step_r8", "k_ais_init_r8", "k_hmc_stepILi5E"):
-            assert k in names, f"{k} is not in the library any more"
-    if stem == "spline_kernels":
-        assert "k_spline_logprob_r8" in names
+    for k in MUST_HOLD.get(stem, ()):
+        assert k in names, f"{k} is not in the library any more"
     bad = {k: v for k, v in res.items() if v}
     assert not bad, bad

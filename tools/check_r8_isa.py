@@ -10,13 +10,15 @@ sys.path.insert(0, ROOT)
 from fab_torch_amd import _isa_check as chk          # noqa: E402
 
 BUILD = os.path.join(ROOT, "fab_torch_amd", "build")
-DEVICE_OBJECTS = ("flow_kernels", "ais_kernels", "spline_kernels", "train_kernels", "reduce_kernels", "resample_scan",
-                  "resample_emit", "weight_decisions", "generic_kernels", "topk")
+AIS_OBJECTS = ("ais_tile16", "ais_tile16_metropolis", "ais_tile48", "ais_moves")       # (ais_driver holds no kernel)
+DEVICE_OBJECTS = ("flow_kernels",) + AIS_OBJECTS + ("spline_kernels", "train_kernels", "reduce_kernels", "resample_scan",
+                                                    "resample_emit", "weight_decisions", "generic_kernels", "topk")
+ALIASES = {"spline": ("spline_kernels",), "flow": AIS_OBJECTS}
 
 
 def main():
     stems = sys.argv[1:] or DEVICE_OBJECTS
-    stems = ["spline_kernels" if s == "spline" else ("ais_kernels" if s == "flow" else s) for s in stems]
+    stems = [t for s in stems for t in ALIASES.get(s, (s,))]
     rc = 0
     for stem in stems:
         obj = os.path.join(BUILD, stem + ".o")
