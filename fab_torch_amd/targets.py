@@ -193,17 +193,25 @@ class ManyWellEnergy(_NativeTarget):
 
 class GMM(_NativeTarget):
     def __init__(self, dim, n_mixes, loc_scaling, log_var_scaling=0.1, seed=0, n_test_set_samples=1000,
-                 use_gpu=True, true_expectation_estimation_n_samples=int(1e7)):
+                 use_gpu=True, true_expectation_estimation_n_samples=int(1e7), locs=None, scales=None):
+        """`locs` / `scales` ([n_mixes, dim] each): the component means and diagonal scales per entry, in place of the
+        reference's random means and one common scale (nothing is drawn then, `loc_scaling` / `log_var_scaling` are unused)."""
         super().__init__()
         self.seed, self.n_mixes, self.dim = seed, n_mixes, dim
         self.n_test_set_samples = n_test_set_samples
         self._true_expectation, self._true_expectation_n = None, int(true_expectation_estimation_n_samples)
-        mean = (torch.rand((n_mixes, dim)) - 0.5) * 2 * loc_scaling          # gmm.py:22 (caller seeds torch)
-        log_var = torch.ones((n_mixes, dim)) * log_var_scaling
+        if locs is not None or scales is not None:
+            if locs is None or scales is None or tuple(locs.shape) != (n_mixes, dim) or tuple(scales.shape) != (n_mixes, dim):
+                raise ValueError(f"GMM: locs and scales must both be given as [{n_mixes}, {dim}] tensors")
+            mean = locs.detach().clone().float().contiguous()
+            diag = scales.detach().clone().float().contiguous()
+        else:
+            mean = (torch.rand((n_mixes, dim)) - 0.5) * 2 * loc_scaling      # gmm.py:22 (caller seeds torch)
+            diag = F.softplus(torch.ones((n_mixes, dim)) * log_var_scaling).contiguous()
         self.register_buffer("cat_probs", torch.ones(n_mixes))
         self.register_buffer("locs", mean)
-        self.register_buffer("scale_trils", torch.diag_embed(F.softplus(log_var)))
-        self.register_buffer("scales", F.softplus(log_var).contiguous())
+        self.register_buffer("scale_trils", torch.diag_embed(diag))
+        self.register_buffer("scales", diag)
         self.device = "cuda" if (use_gpu and torch.cuda.is_available()) else "cpu"
         if self.device == "cuda":
             self.cuda()

@@ -50,11 +50,17 @@ class ManyWell:
 class GMM:
     """Equal-weight diagonal GMM with the reference's -inf mask below -1e4 (gmm.py:57-66)."""
 
-    def __init__(self, dim: int, n_mixes: int, loc_scaling: float, log_var_scaling: float = 0.1,
-                 seed: int = 0):
+    def __init__(self, dim: int, n_mixes: int, loc_scaling: float = 1.0, log_var_scaling: float = 0.1,
+                 seed: int = 0, locs: torch.Tensor = None, scales: torch.Tensor = None):
+        """With `locs` / `scales` ([n_mixes, dim] each, any dtype) the mixture has those means and diagonal scales - what the
+        C ABI's fabhip_target takes per entry; the reference's constructor only ever makes equal scales."""
+        self.dim, self.n_mixes = dim, n_mixes
+        if locs is not None:
+            assert locs.shape == scales.shape == (n_mixes, dim)
+            self.locs, self.scales = locs, scales
+            return
         # experiments/gmm/run.py:53 seeds torch before constructing the target.
         torch.manual_seed(seed)
-        self.dim, self.n_mixes = dim, n_mixes
         self.locs = (torch.rand((n_mixes, dim)) - 0.5) * 2 * loc_scaling            # gmm.py:22
         log_var = torch.ones((n_mixes, dim)) * log_var_scaling                       # gmm.py:23
         self.scales = F.softplus(log_var)                                           # diag of scale_tril, gmm.py:27

@@ -301,12 +301,12 @@ def tuned(D, K, nodes, B, kind, target, dtype=torch.float32):
                 p_accept=[float(t["p_accept"]) for t in h.trace], in_band=in_band, cap=int(in_band.sum()), trace=h.trace)
 
 
-def tol_units(a, b):
-    """per row: the worst element of |a - b| in units of the tolerance of helpers.close (scale of the whole tensor b)."""
+def tol_units(a, b, rtol=RTOL):
+    """per row: the worst element of |a - b| in units of the tolerance of helpers.close at `rtol` (scale of the whole tensor b)."""
     a, b = a.detach().double(), b.detach().double()
     fin = torch.isfinite(b)
     scale = max(1.0, float(b[fin].abs().max()))
-    u = (a - b).abs() / (RTOL * b.abs() + 2e-6 * scale)
+    u = (a - b).abs() / (rtol * b.abs() + 2e-6 * scale)
     u = torch.where(fin, u, torch.zeros_like(u))
     return u.reshape(u.shape[0], -1).amax(1)
 
