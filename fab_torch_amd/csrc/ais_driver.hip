@@ -207,7 +207,7 @@ size_t fabhip_metropolis_workspace_bytes(int64_t B, int32_t dim, int32_t n_updat
 
 int fabhip_metropolis_transition(const fabhip_metropolis_args* a, fabhip_stream_t stream) {
     if (!a || !a->flow.packed || !a->noise_x || !a->noise_u || !a->noise_scalings || !a->workspace || a->B < 0 ||
-        a->n_updates < 1 || a->n_updates > 64)
+        a->n_updates < 1)
         return FABHIP_EINVAL;
     FAB_TRY(check_flow_shape(a->flow.dim, a->flow.n_layers, a->flow.width));
     FAB_TRY(check_target(&a->target, a->flow.dim));

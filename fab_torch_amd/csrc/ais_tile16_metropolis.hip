@@ -94,7 +94,7 @@ __device__ __forceinline__ void metropolis_body(const FlowDims& f, const FlowLds
     const long nv = a.n_valid ? (long)*a.n_valid : a.B;
     const long row0 = (long)blockIdx.x * ROWS;
     if (row0 >= nv) {
-        if (t.tid < a.n_updates) a.part_acc[t.tid * a.nblk + blockIdx.x] = 0.f;
+        for (int n = t.tid; n < a.n_updates; n += NTHREADS) a.part_acc[(long)n * a.nblk + blockIdx.x] = 0.f;
         return;
     }
     float* XC = lds + x.o_XP;        // current positions
@@ -168,14 +168,15 @@ __global__ __launch_bounds__(NTHREADS) void k_metropolis_mix(FlowDims f, FlowLds
 
 __global__ void k_metropolis_adapt(const float* __restrict__ part_acc, int nblk, int n_updates, const int* n_valid,
                                    long B, float* scalings, float target_p_accept, int tune) {
-    const int n = threadIdx.x;
-    if (blockIdx.x != 0 || n >= n_updates || !tune) return;
+    if (blockIdx.x != 0 || !tune) return;
     const long nv = n_valid ? (long)*n_valid : B;
     if (nv <= 0) return;
-    float s = 0.f;
-    for (int i = 0; i < nblk; ++i) s += part_acc[n * nblk + i];
-    const float p_accept = s / (float)nv;
-    scalings[n] = (p_accept > target_p_accept) ? scalings[n] * 1.05f : scalings[n] / 1.05f;
+    for (int n = threadIdx.x; n < n_updates; n += blockDim.x) {     // any number of updates (the reference has no bound)
+        float s = 0.f;
+        for (int i = 0; i < nblk; ++i) s += part_acc[(long)n * nblk + i];
+        const float p_accept = s / (float)nv;
+        scalings[n] = (p_accept > target_p_accept) ? scalings[n] * 1.05f : scalings[n] / 1.05f;
+    }
 }
 
 // Sharded chains: a Metropolis transition whose block sums went into the caller's slab instead of part_acc

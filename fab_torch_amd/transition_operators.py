@@ -350,6 +350,8 @@ class Metropolis(TransitionOperator):
         if noise_u is None:
             noise_u = torch.rand((self.n_updates, B), dtype=torch.float32, device=dev)
         _check_point(point, False)
+        if beta_next is None or float(beta_next) == float(beta):
+            log_w = None        # ais.py:93: left alone (num - den of one expression is NaN, not 0, where a density is not finite)
         if not self.is_native:
             return self._transition_generic(point, i, beta, log_w, beta_next, noise_x.contiguous(), noise_u.contiguous())
         _ops.load().metropolis_transition(

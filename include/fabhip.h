@@ -466,7 +466,7 @@ typedef struct {
     const float* noise_x;    /* [n_updates][B][dim] ~ N(0,1)  (metropolis.py:57) */
     const float* noise_u;    /* [n_updates][B]      ~ U(0,1)  (metropolis.py:65) */
     float* noise_scalings;   /* -> noise_scalings[i-1][0..n_updates), updated    */
-    int32_t n_updates;
+    int32_t n_updates;       /* >= 1, no upper bound (as the reference); every update's scaling is adapted */
     float target_p_accept;
     int32_t tune;            /* adjust_step_size and not eval_mode               */
     void* workspace;
