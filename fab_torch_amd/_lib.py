@@ -78,7 +78,7 @@ class AisArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-TARGET_MANYWELL, TARGET_GMM = 1, 2
+TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC = 1, 2, 3
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
 
 _lib = None
@@ -125,7 +125,7 @@ SYMBOLS = [
     "fabhip_resample_stratified_workspace_bytes", "fabhip_resample_stratified",
     "fabhip_next_beta", "fabhip_log_w_first",
 ]
-ABI_VERSION = 223          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 224          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):

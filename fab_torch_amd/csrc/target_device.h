@@ -1,6 +1,7 @@
 // Device-side target log-densities evaluated on the 16-chain tile of a workgroup.
 // ManyWell: fab/target_distributions/many_well.py:81-90 -> double_well.py:44-58
 // GMM:      fab/target_distributions/gmm.py:57-66 (MixtureSameFamily of diagonal normals, -inf mask)
+// Quartic:  log p = -sum_j (a_j x_j + b_j x_j^2 + c_j x_j^4) - 1/2 x^T J x - log_norm, J symmetric (tests/quartic_cases.py)
 #pragma once
 #include "flow_device.h"
 
@@ -26,6 +27,8 @@ static inline int check_target(const fabhip_target* t, int dim) {
     if (t->dim != dim) return FABHIP_EINVAL;
     if (t->kind == FABHIP_TARGET_MANYWELL) return (dim % 2 == 0) ? FABHIP_OK : FABHIP_EINVAL;
     if (t->kind == FABHIP_TARGET_GMM) return (t->n_mix > 0 && t->locs && t->scales) ? FABHIP_OK : FABHIP_EINVAL;
+    if (t->kind == FABHIP_TARGET_QUARTIC)
+        return (t->locs && t->scales && dim >= 1 && dim <= FABHIP_MAX_DIM) ? FABHIP_OK : FABHIP_EINVAL;
     return FABHIP_ENOTSUP;
 }
 
@@ -57,6 +60,29 @@ __device__ float target_tile(const TargetDev& tg, const float* X, int ldx, float
             }
             acc += -e;
             if (GRAD) GP[t.row * ldg + j] = g;
+        }
+        return row16_sum(acc) - tg.log_norm;
+    }
+    if (tg.kind == FABHIP_TARGET_QUARTIC) {
+        // Lane c owns sites j = c, c + 16, ... (D <= 64: at most four).  J = locs [D][D] is symmetric, so (J x)_j is read as
+        // sum_k J[k][j] x_k in ascending k: the 16 lanes of a row read consecutive floats of row k, x_k is an LDS broadcast.
+        // The site loop is rolled as ManyWell's and the k loop sits INSIDE it, unrolled by 4 only: a lane walks one column of J
+        // per site it owns (every element of J is read once per row; the row's x is re-read from LDS once per owned site), and
+        // the live state is one accumulator and the four loads in flight.  (k outer with the four site accumulators live cost the HMC kernels 12 - 24 VGPRs and
+        // one of them scratch: DESIGN section 18.)
+        const float* J = tg.locs;
+        const float* S = tg.scales;            // [3][D]: rows a, b, c
+        float acc = 0.f;
+#pragma unroll 1
+        for (int j = t.c; j < D; j += 16) {
+            float jx = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < D; ++k) jx += J[k * D + j] * X[t.row * ldx + k];
+            const float x = X[t.row * ldx + j];
+            const float x2 = x * x;
+            const float sa = S[j], sb = S[D + j], sc = S[2 * D + j];
+            acc += -(sa * x + sb * x2 + sc * (x2 * x2) + 0.5f * x * jx);
+            if (GRAD) GP[t.row * ldg + j] = -(sa + 2.f * sb * x + 4.f * sc * (x2 * x)) - jx;
         }
         return row16_sum(acc) - tg.log_norm;
     }

@@ -117,8 +117,9 @@ void fill_params(fabhip_flow_params& p, at::TensorList params, int64_t dim, int6
         }
 }
 
+// `ref`: the tensor whose device the launch is enqueued for (the quartic target's tensors must live there).
 fabhip_target make_target(int64_t kind, at::ArrayRef<double> prm, const optional<Tensor>& locs,
-                          const optional<Tensor>& scales, int64_t dim) {
+                          const optional<Tensor>& scales, int64_t dim, const Tensor& ref) {
     TORCH_CHECK(prm.size() == 4, "fabhip: target parameters are {a, b, c, log_norm}");
     fabhip_target t;
     t.kind = (int32_t)kind; t.dim = (int32_t)dim;
@@ -129,6 +130,16 @@ fabhip_target make_target(int64_t kind, at::ArrayRef<double> prm, const optional
         t.locs = fp(*locs, "locs"); t.scales = fp(*scales, "scales");
         t.n_mix = (int32_t)locs->size(0);
         TORCH_CHECK(locs->dim() == 2 && locs->size(1) == dim && scales->sizes() == locs->sizes(), "fabhip: GMM shapes");
+    }
+    if (kind == FABHIP_TARGET_QUARTIC) {      // locs = coupling J [D, D] (symmetric), scales = site coefficients [3, D]
+        TORCH_CHECK(locs.has_value() && scales.has_value(), "fabhip: quartic target needs the coupling (locs) and the site "
+                    "coefficients (scales)");
+        TORCH_CHECK(dim >= 1 && dim <= FABHIP_MAX_DIM, "fabhip: quartic target needs 1 <= dim <= ", FABHIP_MAX_DIM, ", got ", dim);
+        TORCH_CHECK(locs->dim() == 2 && locs->size(0) == dim && locs->size(1) == dim, "fabhip: quartic coupling must be [",
+                    dim, ", ", dim, "], got ", locs->sizes());
+        TORCH_CHECK(scales->dim() == 2 && scales->size(0) == 3 && scales->size(1) == dim, "fabhip: quartic site coefficients "
+                    "must be [3, ", dim, "], got ", scales->sizes());
+        t.locs = fpn(*locs, dim * dim, ref, "quartic coupling"); t.scales = fpn(*scales, 3 * dim, ref, "quartic site coefficients");
     }
     return t;
 }
@@ -535,7 +546,7 @@ std::tuple<Tensor, Tensor> target_logp_grad(int64_t kind, at::ArrayRef<double> p
                                             const optional<Tensor>& scales, const Tensor& x, bool with_grad) {
     c10::DeviceGuard g(x.device());
     TORCH_CHECK(x.dim() == 2, "fabhip: x must be [B, dim]");
-    const fabhip_target t = make_target(kind, prm, locs, scales, x.size(1));
+    const fabhip_target t = make_target(kind, prm, locs, scales, x.size(1), x);
     const int64_t B = x.size(0);
     Tensor lp = fempty({B}, x), grad = with_grad ? at::empty_like(x) : fempty({0}, x);
     chk(fabhip_target_log_prob(&t, fp(x, "x"), lp.data_ptr<float>(), with_grad ? grad.data_ptr<float>() : nullptr, B,
@@ -560,7 +571,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> create_point(const Tensor& packed, in
                                                         const Tensor& x, bool with_grad, int64_t precision) {
     c10::DeviceGuard g(x.device());
     const fabhip_flow f = make_flow(packed, dim, n_layers, width, precision);
-    const fabhip_target t = make_target(kind, prm, locs, scales, dim);
+    const fabhip_target t = make_target(kind, prm, locs, scales, dim, packed);
     TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
     const int64_t B = x.size(0);
     Tensor lq = fempty({B}, x), lp = fempty({B}, x);
@@ -584,7 +595,7 @@ void hmc_transition(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t
     c10::DeviceGuard g(x.device());
     fabhip_hmc_args a;
     a.flow = make_flow(packed, dim, n_layers, width, precision);
-    a.target = make_target(kind, prm, locs, scales, dim);
+    a.target = make_target(kind, prm, locs, scales, dim, packed);
     TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
     const int64_t B = x.size(0), n_outer = epsilons_row.numel();
     TORCH_CHECK(noise_p.numel() == n_outer * B * dim && noise_e.numel() == n_outer * B, "fabhip: HMC noise shapes");
@@ -617,7 +628,7 @@ void metropolis_transition(const Tensor& packed, int64_t dim, int64_t n_layers, 
     c10::DeviceGuard g(x.device());
     fabhip_metropolis_args a;
     a.flow = make_flow(packed, dim, n_layers, width);
-    a.target = make_target(kind, prm, locs, scales, dim);
+    a.target = make_target(kind, prm, locs, scales, dim, packed);
     TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
     const int64_t B = x.size(0), n_updates = noise_scalings_row.numel();
     TORCH_CHECK(noise_x.numel() == n_updates * B * dim && noise_u.numel() == n_updates * B,
@@ -722,7 +733,7 @@ void spline_hmc_transition(const Tensor& packed, int64_t dim, int64_t n_layers, 
                            optional<Tensor> avg_distance, int64_t precision) {
     c10::DeviceGuard g(x.device());
     const fabhip_spline_flow f = make_spline(packed, dim, n_layers, hidden, precision);
-    const fabhip_target tg = make_target(kind, prm, locs, scales, dim);
+    const fabhip_target tg = make_target(kind, prm, locs, scales, dim, packed);
     TORCH_CHECK(x.dim() == 2, "fabhip: x must be [B, dim]");
     const int64_t B = x.size(0), D = x.size(1);
     TORCH_CHECK(D == dim && n_outer >= 1 && n_leap >= 1, "fabhip: spline_hmc_transition shapes");
@@ -789,7 +800,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     c10::DeviceGuard g(eps0.device());
     fabhip_spline_ais_args a;
     a.flow = make_spline(packed, dim, n_layers, hidden, precision);
-    a.target = make_target(kind, prm, locs, scales, dim);
+    a.target = make_target(kind, prm, locs, scales, dim, packed);
     TORCH_CHECK(eps0.dim() == 2 && eps0.size(1) == dim, "fabhip: eps0 must be [B, dim]");
     const int64_t B = eps0.size(0), M = (int64_t)betas.size() - 2;
     TORCH_CHECK(M >= 1 && n_outer >= 1 && L >= 1, "fabhip: spline_ais_run needs M, n_outer, L >= 1");
@@ -904,7 +915,7 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
                    bool smc_on) {
     fabhip_ais_args& a = c.a;
     a.flow = make_flow(packed, dim, n_layers, width, precision);
-    a.target = make_target(kind, prm, locs, scales, dim);
+    a.target = make_target(kind, prm, locs, scales, dim, packed);
     const int64_t M = (int64_t)betas.size() - 2;
     const bool hmc = transition == FABHIP_TRANSITION_HMC;
     TORCH_CHECK(M >= 1, "fabhip: betas must hold M + 2 values");

@@ -1,6 +1,7 @@
 """Target distributions of the hot path: ManyWell (fab/target_distributions/many_well.py:16-90,
 double_well.py:31-58) and the 40-mode GMM (fab/target_distributions/gmm.py:12-66) — same constructor
-arguments and `log_prob` semantics; `log_prob` runs csrc/target_device.h on the GPU."""
+arguments and `log_prob` semantics; `log_prob` runs csrc/target_device.h on the GPU.  `CoupledQuarticEnergy` / `LatticePhi4`: the
+coupled-quartic family (no counterpart in the reference; tests/quartic_cases.py is its definition)."""
 import math
 
 import numpy as np
@@ -269,3 +270,155 @@ class GMM(_NativeTarget):
                     "ess_over_p": effective_sample_size_over_p(log_p_test - log_q_test).item(),
                     "kl_forward": torch.mean(log_p_test - log_q_test).item()}
         return {"bias_normed": bias_normed.item(), "bias_no_correction": torch.abs(bias_no_correction).item()}
+
+
+class CoupledQuarticEnergy(_NativeTarget):
+    """Quartic sites with a symmetric quadratic coupling,
+        log p(x) = - sum_j (a_j x_j + b_j x_j^2 + c_j x_j^4) - 1/2 x^T J x - log_norm,   D <= 64,
+    evaluated by the third branch of csrc/target_device.h on every route of the fused path: lattice phi^4 (`LatticePhi4`),
+    coupled double wells, soft-spin glasses, correlated Gaussians (c = 0) and ManyWell itself (J = 0).  The definition is
+    tests/quartic_cases.py.  The constructor works in float64 on the host; the device holds float32 copies."""
+
+    MAX_DIM = 64                                                    # FABHIP_MAX_DIM
+
+    def __init__(self, site_a, site_b, site_c, coupling, normalised: bool = False, use_gpu: bool = True):
+        super().__init__()
+        name = type(self).__name__
+        a, b, c, J = (torch.as_tensor(v).detach().to("cpu", torch.float64) for v in (site_a, site_b, site_c, coupling))
+        if a.dim() != 1 or a.shape[0] < 1 or b.shape != a.shape or c.shape != a.shape or tuple(J.shape) != (a.shape[0],) * 2:
+            raise ValueError(f"{name}: site_a, site_b, site_c must be [D] and coupling [D, D], got {tuple(a.shape)}, "
+                             f"{tuple(b.shape)}, {tuple(c.shape)} and {tuple(J.shape)}")
+        D = int(a.shape[0])
+        if D > self.MAX_DIM:
+            raise ValueError(f"{name}: dim = {D} is above the {self.MAX_DIM} sites the kernels hold")
+        if not all(bool(torch.isfinite(v).all()) for v in (a, b, c, J)):
+            raise ValueError(f"{name}: a coefficient or a coupling is not finite")
+        if float((J - J.T).abs().max()) > 1e-6 * float(J.abs().max()):
+            raise ValueError(f"{name}: the coupling is not symmetric (the kernels read J[k][j] for (J x)_j)")
+        J = 0.5 * (J + J.T)
+        if bool((c < 0).any()):
+            raise ValueError(f"{name}: site_c must be >= 0 (the density could not be normalised)")
+        flat = c == 0                                               # no quartic wall there: the quadratic form must hold them
+        if bool(flat.any()):
+            P = (2.0 * torch.diag(b) + J)[flat][:, flat]
+            if float(torch.linalg.eigvalsh(P).min()) <= 0.0:
+                raise ValueError(f"{name}: the density cannot be normalised: 2 diag(site_b) + coupling is not positive "
+                                 "definite on the sites with site_c = 0")
+        self.dim, self.normalised = D, bool(normalised)
+        self._a64, self._b64, self._c64, self._J64 = a, b, c, J
+        self.register_buffer("coupling", J.float().contiguous())                       # fabhip_target.locs   [D][D]
+        self.register_buffer("site_coefs", torch.stack([a, b, c]).float().contiguous())    # fabhip_target.scales [3][D]
+        self._log_Z = None
+        if self.normalised:
+            self.log_Z                                                # raises where no exact constant exists
+        self.device = "cuda" if (use_gpu and torch.cuda.is_available()) else "cpu"
+        if self.device == "cuda":
+            self.cuda()
+
+    # ---- the two exact cases --------------------------------------------------------------------------------------------------
+    @property
+    def is_gaussian(self) -> bool:
+        return bool((self._c64 == 0).all())
+
+    @property
+    def is_independent(self) -> bool:
+        return bool((self._J64 - torch.diag(torch.diagonal(self._J64)) == 0).all())
+
+    def _precision(self):
+        return 2.0 * torch.diag(self._b64) + self._J64
+
+    @staticmethod
+    def _site_log_z(a, b, c):
+        """log of the integral of exp(-(a x + b x^2 + c x^4)) over the line (float64; trapezoid rule on a range beyond which
+        the integrand is below exp(-60) of its peak - it converges geometrically for such integrands)."""
+        if c == 0.0:
+            return 0.5 * math.log(math.pi / b) + a * a / (4.0 * b)
+        R = 1.0
+        while c * R ** 4 - abs(b) * R * R - abs(a) * R < 60.0 + abs(b) ** 2 / (4.0 * c) + abs(a):
+            R *= 1.25
+        x = torch.linspace(-R, R, 400001, dtype=torch.float64)
+        e = -(a * x + b * x * x + c * x ** 4)
+        return float(torch.logsumexp(e, 0) + math.log(2.0 * R / (x.numel() - 1)))
+
+    @property
+    def log_Z(self) -> torch.Tensor:
+        """float64: all c_j = 0 (Gaussian, P = 2 diag(b) + J: D/2 log 2 pi - 1/2 log det P + 1/2 a^T P^-1 a) or J diagonal
+        (independent sites with the diagonal folded into b, one quadrature per site); no exact constant otherwise."""
+        if self._log_Z is None:
+            a, b, c = self._a64, self._b64, self._c64
+            if self.is_gaussian:
+                P = self._precision()
+                v = 0.5 * self.dim * math.log(2.0 * math.pi) - 0.5 * torch.linalg.slogdet(P)[1] + 0.5 * a @ torch.linalg.solve(P, a)
+            elif self.is_independent:
+                be = b + 0.5 * torch.diagonal(self._J64)
+                v = sum(self._site_log_z(float(a[j]), float(be[j]), float(c[j])) for j in range(self.dim))
+            else:
+                raise NotImplementedError(f"{type(self).__name__}: log_Z is known for c = 0 and for a diagonal coupling only")
+            self._log_Z = torch.as_tensor(v, dtype=torch.float64)
+        return self._log_Z
+
+    @property
+    def Z(self):
+        return torch.exp(self.log_Z)
+
+    def native_target(self):
+        log_norm = float(self.log_Z) if self.normalised else 0.0
+        return _ops.TARGET_QUARTIC, [0.0, 0.0, 0.0, log_norm], self.coupling, self.site_coefs
+
+    def log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        return _target_log_prob(self, x)
+
+    def energy(self, x, temperature=None):
+        assert x.shape[-1] == self.dim, "`x` does not match `dim`"
+        return -self.log_prob(x)[..., None] / (1.0 if temperature is None else temperature)
+
+    def force(self, x, temperature=None):
+        assert x.shape[-1] == self.dim, "`x` does not match `dim`"
+        _, g = self.log_prob_and_grad(x.detach().contiguous().float())
+        return g / (1.0 if temperature is None else temperature)
+
+    def sample(self, shape) -> torch.Tensor:
+        """Exact samples of the Gaussian case: mean -P^-1 a, covariance P^-1 (Cholesky)."""
+        if not self.is_gaussian:
+            raise NotImplementedError(f"{type(self).__name__}: exact samples exist for c = 0 only")
+        assert len(shape) == 1
+        P = self._precision()
+        cov = torch.linalg.inv(P)
+        chol = torch.linalg.cholesky(0.5 * (cov + cov.T))
+        mean = -torch.linalg.solve(P, self._a64)
+        dev = self.coupling.device
+        z = torch.randn(int(shape[0]), self.dim, device=dev)
+        return mean.float().to(dev) + z @ chol.T.float().to(dev)
+
+
+class LatticePhi4(CoupledQuarticEnergy):
+    """Lattice phi^4 on a periodic lattice of prod(shape) <= 64 sites, any number of dimensions:
+        S = sum_x [(1 - 2 lam) phi_x^2 + lam phi_x^4] - 2 kappa sum_x sum_mu phi_x phi_(x + mu),   log p = -S.
+    a = 0, b = 1 - 2 lam, c = lam; J_xy = -2 kappa times the bonds joining x and y as the sum over (x, mu) meets them: an extent
+    of 2 joins two sites twice, an extent of 1 joins a site to itself (both ends of that bond sit on the diagonal)."""
+
+    def __init__(self, shape, kappa: float, lam: float, normalised: bool = False, use_gpu: bool = True):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) < 1 or any(s < 1 for s in shape):
+            raise ValueError(f"LatticePhi4: shape must hold positive extents, got {shape}")
+        D = int(np.prod(shape))
+        if D > self.MAX_DIM:
+            raise ValueError(f"LatticePhi4: {shape} has {D} sites, above the {self.MAX_DIM} the kernels hold")
+        idx = np.arange(D).reshape(shape)
+        J = torch.zeros(D, D, dtype=torch.float64)
+        for mu in range(len(shape)):
+            x, y = torch.as_tensor(idx.reshape(-1)), torch.as_tensor(np.roll(idx, -1, axis=mu).reshape(-1))
+            J.index_put_((x, y), torch.full((D,), -2.0 * kappa, dtype=torch.float64), accumulate=True)
+            J.index_put_((y, x), torch.full((D,), -2.0 * kappa, dtype=torch.float64), accumulate=True)
+        super().__init__(torch.zeros(D, dtype=torch.float64), torch.full((D,), 1.0 - 2.0 * lam, dtype=torch.float64),
+                         torch.full((D,), float(lam), dtype=torch.float64), J, normalised=normalised, use_gpu=use_gpu)
+        self.shape, self.kappa, self.lam = shape, float(kappa), float(lam)
+
+    def performance_metrics(self, samples, log_w, log_q_fn=None, batch_size=None):
+        """Importance-weighted <|M|>, <M^2> and the weighted share of M > 0, M the mean field of a sample: the share is the Z2
+        balance (1/2 for the symmetric density; 0 or 1 when the sampler has collapsed onto one of the two modes)."""
+        del log_q_fn, batch_size
+        m = samples.double().mean(-1)
+        w = torch.softmax(log_w.double(), 0)
+        return {"abs_magnetisation": float((w * m.abs()).sum()), "magnetisation_sq": float((w * m * m).sum()),
+                "positive_share": float((w * (m > 0).double()).sum())}

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 223
+#define FABHIP_ABI_VERSION 224
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -365,15 +365,19 @@ int fabhip_train_step_plan(int32_t dim, int32_t n_layers, int32_t width, int64_t
 /* ------------------------------------------------------------------------------------------
  * Targets (fab/target_distributions/many_well.py:81-90, double_well.py:44-58, gmm.py:57-66)
  * ---------------------------------------------------------------------------------------- */
-enum { FABHIP_TARGET_MANYWELL = 1, FABHIP_TARGET_GMM = 2 };
+/* FABHIP_TARGET_QUARTIC (ABI 224): coupled quartic sites (lattice phi^4, coupled double wells, correlated Gaussians),
+ *   log p(x) = - sum_j (a_j x_j + b_j x_j^2 + c_j x_j^4) - 1/2 sum_j x_j (J x)_j - log_norm,   1 <= dim <= FABHIP_MAX_DIM,
+ * with J SYMMETRIC (the kernels read J[k][j] for (J x)_j and do not check it).  NaN / inf coordinates propagate. */
+enum { FABHIP_TARGET_MANYWELL = 1, FABHIP_TARGET_GMM = 2, FABHIP_TARGET_QUARTIC = 3 };
 
 typedef struct {
     int32_t kind, dim;
     float a, b, c;       /* many well: energy a x + b x^2 + c x^4 on even dims, x^2/2 on odd     */
-    float log_norm;      /* subtracted from log p (0 unless `normalised`)                        */
-    int32_t n_mix;       /* GMM: number of equally weighted components                           */
-    const float* locs;   /* GMM: [n_mix][dim]                                                    */
-    const float* scales; /* GMM: [n_mix][dim] diagonal of scale_tril                             */
+    float log_norm;      /* subtracted from log p (0 unless `normalised`); many well and quartic */
+    int32_t n_mix;       /* GMM: number of equally weighted components; unused otherwise         */
+    const float* locs;   /* GMM: [n_mix][dim]; quartic: the coupling J, [dim][dim], symmetric    */
+    const float* scales; /* GMM: [n_mix][dim] diagonal of scale_tril; quartic: the site          */
+                         /* coefficients [3][dim], rows a, b, c                                  */
 } fabhip_target;
 
 int fabhip_target_log_prob(const fabhip_target* target, const float* x, float* log_p, float* grad_x,
