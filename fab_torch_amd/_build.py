@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libfabhip.so")
 SOURCES = ["flow_kernels.hip", "ais_tile16.hip", "ais_tile16_metropolis.hip", "ais_tile48.hip", "ais_moves.hip", "ais_driver.hip", "reduce_kernels.hip", "resample_scan.hip", "resample_emit.hip",
-           "weight_decisions.hip", "train_kernels.hip", "topk.hip", "generic_kernels.hip", "spline_kernels.hip", "train_step.hip"]
+           "weight_decisions.hip", "train_kernels.hip", "topk.hip", "generic_kernels.hip", "spline_pack.hip", "spline_tile16.hip", "spline_stream.hip", "train_step.hip"]
 ARCH = "gfx950"
 # -amdgpu-mfma-vgpr-form (round 6): MFMA accumulators in ARCHITECTURAL registers.  hipcc's default puts them in the accumulation
 # file, whose only tenant here should be the weight rings (inline-asm loads): every epilogue then starts with one v_accvgpr_read

@@ -251,7 +251,7 @@ static int phase_tail(const fabhip_point& point, float* log_w, long B, int dim, 
     return check_launch();
 }
 
-// ---- spline flow as base distribution (csrc/spline_kernels.hip) ------------------------------------------------------
+// ---- spline flow as base distribution (csrc/spline_stream.hip, spline_tile16.hip) ------------------------------------------------------
 size_t fabhip_spline_hmc_workspace_bytes(int32_t dim, int32_t n_layers, int32_t hidden, int64_t B) {
     return carve_spline_hmc_ws(nullptr, dim, n_layers, hidden, B).bytes;
 }

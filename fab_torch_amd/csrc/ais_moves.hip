@@ -274,7 +274,7 @@ __global__ void k_sub(const float* __restrict__ a, const float* __restrict__ b, 
 
 }  // namespace fab
 
-// ---- spline flow as base distribution (csrc/spline_kernels.hip) ------------------------------------------------------
+// ---- spline flow as base distribution (csrc/spline_stream.hip, spline_tile16.hip) ------------------------------------------------------
 // (C linkage: the symbol has always been the plain name)
 extern "C" __global__ void k_spline_init_logw(const float* __restrict__ lq, const float* __restrict__ lp, const float* __restrict__ lq0,
                                    fabhip_anneal an, float* __restrict__ log_w, float* __restrict__ base_log_w, long n) {

@@ -38,7 +38,7 @@ int gen_hmc_accept(const fabhip_point* prop, const fabhip_point* cur, long B, in
 
 // the transition state inside a generic-HMC workspace (generic_kernels.hip)
 void gen_hmc_state(void* workspace, long B, int dim, float** XP, float** P, float** GU);
-// One leapfrog of the spline family in ONE launch (spline_kernels.hip; r4): first half step, spline density + gradient, target
+// One leapfrog of the spline family in ONE launch (spline_stream.hip; r4): first half step, spline density + gradient, target
 // + gradient and second half step inside k_spline_logprob_r8.  FABHIP_ENOTSUP where that kernel does not apply (the caller
 // then runs the four launches of the generic pieces - the same arithmetic, bit for bit).
 // Round 5: the rest of the outer step inside the leapfrog launches (spline_r8.h) - flags & 1: first leapfrog of the outer step

@@ -25,19 +25,19 @@
 // Everything else a layer needs (metadata rows, unconditional spline parameters, periodic-feature weights, biases) is one
 // contiguous head block per layer, copied to LDS at the layer top with plain loads BEFORE the ring is requested, so no
 // compiler-tracked load ever waits behind the stream.  ReLU decisions: one 64-bit ballot per (wave, chain), kept in LDS.
-// Included from spline_kernels.hip (namespace fab, after the rqs_* helpers); the stream / GEMM-step machinery is stream_r8.h.
+// Included by spline_stream.hip (behind its `#pragma clang fp contract(off)`); the image's layout and the spline element functions
+// are spline_device.h, the stream / GEMM-step machinery stream_r8.h, the image's pack kernel k_spline_pack_r8 in spline_pack.hip.
+#pragma once
+#include "flow_device.h"
+#include "target_device.h"
+#include "stream_r8.h"
+#include "launch.h"
+#include "spline_device.h"
+
+namespace fab {
 
 constexpr int S8_AS = 64 + 4;          // leading dim of the identity-feature tile (K = 64)
 constexpr int S8_WS = 256 + 4;         // leading dim of the hidden tiles
-
-// head block of a layer in the r8 image (floats); the first three regions sit where SplineDims puts them in a layer image
-constexpr int S8H_META = 0, S8H_UNC = (SP_META_ROWS + 2) * 64, S8H_PFW = S8H_UNC + 1664, S8H_B0 = S8H_PFW + 128,
-              S8H_BA = S8H_B0 + 256, S8H_BB = S8H_BA + 256, S8H_NXT = S8H_BB + 256, S8H_BF = S8H_NXT + 128;
-
-static_assert(S8H_BF == (SP_META_ROWS + 2) * 64 + 1664 + 128 + 3 * 256 + 128, "make_spline_dims: r8_head");
-FAB_HD int s8_head_floats(const SplineDims& f) { return f.r8_head; }                      // S8H_BF + NFP: a multiple of 128
-FAB_HD int s8_tiles_per_wave(const SplineDims& f) { return f.r8_tpl; }                    // per layer and direction: 16 + 64 (2 + NCH)
-FAB_HD long s8_layer_floats(const SplineDims& f) { return f.r8_layer; }
 
 struct S8Lds {
     int PS;                            // leading dim of the conditioner-output tile
@@ -98,80 +98,6 @@ __device__ __forceinline__ void s8_gemm64(S8Stream& s, const float* act, int lda
     s8_iter<32, 32, PHASE, S8_INF>(s, ap, 4 * lda, acc);
     s8_iter<32, 32, PHASE, LAST>(s, ap + 128, 4 * lda, acc);
     s8_fold(acc, o);
-}
-
-// ---- image -----------------------------------------------------------------------------------------------------------
-// Layer block of the r8 image: [head | forward tiles: wave 0 .. 3 | reverse tiles: wave 0 .. 3], a wave's tiles in stream order.
-__global__ __launch_bounds__(256) void k_spline_pack_r8(SplineDims f, SplineSrc s, const float* __restrict__ prev_meta,
-                                                        int layer, float* __restrict__ packed) {
-    const int H = s8_head_floats(f), TPL = s8_tiles_per_wave(f);
-    const long total = s8_layer_floats(f);
-    float* __restrict__ dst = packed + f.o_r8 + (size_t)layer * total;
-    const int n_id = (int)s.meta[M_CNT * 64 + 0], n_tr = (int)s.meta[M_CNT * 64 + 1], n_pf = (int)s.meta[M_CNT * 64 + 2];
-    const int W = f.W, nout = n_tr * SP_NP;
-    for (long off = (long)blockIdx.x * blockDim.x + threadIdx.x; off < total; off += (long)gridDim.x * blockDim.x) {
-        float v = 0.f;
-        if (off < H) {
-            const int e = (int)off;
-            if (e < SP_META_ROWS * 64) v = s.meta[e];
-            else if (e < S8H_UNC) {                                            // M_POSID / M_POSTR (k_spline_pack_layer)
-                const int q = e - SP_META_ROWS * 64, row = q >> 6, j = q & 63;
-                const int cnt = row == 0 ? n_id : n_tr;
-                const float* feats = s.meta + (row == 0 ? M_IDF : M_TRF) * 64;
-                v = -1.f;
-                for (int i = 0; i < cnt; ++i) if ((int)feats[i] == j) v = (float)i;
-            } else if (e < S8H_PFW) {
-                const int q = e - S8H_UNC, i = q / SP_NP, p = q % SP_NP;
-                if (i < n_id && q < SP_MD * SP_NP)
-                    v = p < SP_K ? s.uw[i * SP_K + p] : (p < 2 * SP_K ? s.uh[i * SP_K + p - SP_K] : s.ud[i * (SP_K + 1) + p - 2 * SP_K]);
-            } else if (e < S8H_B0) { const int q = e - S8H_PFW; if (q < 2 * n_pf) v = s.pfw[q]; }
-            else if (e < S8H_BA) { const int j = e - S8H_B0; if (j < W) v = s.b0[j]; }
-            else if (e < S8H_BB) { const int j = e - S8H_BA; if (j < W) v = s.ba[j]; }
-            else if (e < S8H_NXT) { const int j = e - S8H_BB; if (j < W) v = s.bb[j]; }
-            else if (e < S8H_BF) {                                             // pre-shift of the NEXT stage (layer - 1): shift | on
-                const int q = e - S8H_NXT;
-                if (prev_meta) v = prev_meta[(q < 64 ? M_PRESH : M_PREON) * 64 + (q & 63)];
-            } else { const int j = e - S8H_BF; if (j < nout) v = s.bf[j]; }
-        } else {
-            const long e = off - H;
-            const int kk = (int)(e & 3), lane = (int)((e >> 2) & 63);
-            const long tl = e >> 8;
-            const int tile = (int)(tl % TPL), wave = (int)((tl / TPL) % NWAVE), dir = (int)(tl / ((long)TPL * NWAVE));
-            const int n = 64 * wave + lane;
-            // round 5 (f.r8_trim): the stream without zero tiles - W0 as K0Q = 4 k-quads, WfT as KFQ = 100, W0T as 4 dense tiles
-            const int K0Q = f.r8_trim ? 4 : 16, KFQ = f.r8_trim ? 100 : 64 * f.NCH;
-            if (dir == 0) {
-                if (tile < K0Q) {                                              // W0: B[k][n] = w0[n][k]
-                    const int k = 4 * tile + kk;
-                    if (k < n_id && n < W) v = s.w0[n * n_id + k];
-                } else if (tile < K0Q + 64 * (2 + f.NCH)) {
-                    const int t2 = tile - K0Q, m = t2 >> 6, k = 4 * (t2 & 63) + kk;
-                    if (m == 0) { if (k < W && n < W) v = s.wa[n * W + k]; }
-                    else if (m == 1) { if (k < W && n < W) v = s.wb[n * W + k]; }
-                    else { const int col = (m - 2) * 256 + n; if (k < W && col < nout) v = s.wf[col * W + k]; }
-                }
-            } else {
-                if (tile < KFQ) {                                              // WfT: B[k][n] = wf[k][n]
-                    const int k = 4 * tile + kk;
-                    if (k < nout && n < W) v = s.wf[k * W + n];
-                } else {
-                    const int t2 = tile - KFQ;
-                    if (t2 < 64) { const int k = 4 * t2 + kk; if (k < W && n < W) v = s.wb[k * W + n]; }
-                    else if (t2 < 128) { const int k = 4 * (t2 - 64) + kk; if (k < W && n < W) v = s.wa[k * W + n]; }
-                    else if (!f.r8_trim) {                                     // W0T, K split over the waves: B[k][i] = w0[k][i]
-                        if (t2 < 144) {
-                            const int k = 64 * wave + 4 * (t2 - 128) + kk;
-                            if (k < W && lane < n_id) v = s.w0[k * n_id + lane];
-                        }
-                    } else if (t2 < 132) {                                     // ... as dense tiles: 4 k-quads x 16 identity features
-                        const int k = 64 * wave + 4 * (4 * (t2 - 128) + (lane >> 4)) + kk, c = lane & 15;
-                        if (k < W && c < n_id) v = s.w0[k * n_id + c];
-                    }
-                }
-            }
-        }
-        dst[off] = v;
-    }
 }
 
 // optional leapfrog around the density evaluation (launch.h: SplineLeap; XP == nullptr: a plain density call)
@@ -740,3 +666,5 @@ __global__ __launch_bounds__(NTHREADS) void k_spline_logprob_r8(SplineDims f, S8
     }
 #undef S8_TL
 }
+
+}  // namespace fab

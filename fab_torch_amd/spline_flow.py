@@ -1,4 +1,4 @@
-"""Circular / linear-tail rational-quadratic spline coupling flow backed by the HIP kernels of csrc/spline_kernels.hip.
+"""Circular / linear-tail rational-quadratic spline coupling flow backed by the HIP kernels of csrc/spline_*.hip.
 
 Host-side mirror of what the reference builds with normflows for alanine dipeptide
 (experiments/make_flow/make_aldp_model.py:57-71,121-134,146-167, `flow.type = circular-coup-nsf`,

@@ -225,7 +225,7 @@ def test_spline_flow_module_has_normflows_keys_and_fails_loudly_on_the_cpu():
 
 
 def test_workspace_sizes_are_the_recorded_ones():
-    """Every *_workspace_bytes of the AIS units against tests/golden/workspace_bytes.json (host-only functions).  The sizes come
+    """Every *_workspace_bytes of the AIS and spline units against tests/golden/workspace_bytes.json (host-only functions).  The sizes come
     out of the carve functions that also hand the drivers their pointers: a block added to one layout shows up here."""
     import itertools
     import json
@@ -235,7 +235,9 @@ def test_workspace_sizes_are_the_recorded_ones():
     i32, i64 = C.c_int32, C.c_int64
     realnvp = list(itertools.product([1, 15, 16, 17, 1024, 1152, 1153, 2048, 2049, 4096, 32769], [2, 6, 32, 33, 64], [1, 2, 5]))
     spline = [s + (B,) for s, B in itertools.product([(6, 4, 64), (60, 12, 256)], [16, 1000, 2048])]
+    spline_ws = [s + (B, g) for s, B, g in itertools.product([(6, 4, 64), (24, 2, 256), (60, 12, 256)], [1, 16, 17, 1000, 2048], [0, 1])]
     grids = {"fabhip_hmc_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_spline_workspace_bytes": ([i32, i32, i32, i64, i32], spline_ws),
              "fabhip_metropolis_workspace_bytes": ([i64, i32, i32], realnvp),
              "fabhip_ais_workspace_bytes": ([i64, i32, i32], realnvp),
              "fabhip_ais_smc_workspace_bytes": ([i64, i32, i32], realnvp),
@@ -250,3 +252,25 @@ def test_workspace_sizes_are_the_recorded_ones():
         assert sorted(want) == sorted(cases), f"{name}: the fixture does not hold the cases of this test"
         got = {c: fn(*c) for c in cases}
         assert got == want, {c: (got[c], want[c]) for c in cases if got[c] != want[c]}
+
+
+def test_spline_image_and_tape_layouts_are_the_recorded_ones():
+    """fabhip_spline_packed_floats and all 16 words of fabhip_spline_tape_layout against tests/golden/spline_layout.json: the
+    image and the tape are read by offset on both sides of the C ABI (spline_flow.py slices the tape), so a moved block shows here."""
+    import itertools
+    import json
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "spline_layout.json")) as fh:
+        rec = json.load(fh)
+    shapes = [(6, 4, 64), (24, 2, 256), (60, 12, 256)]
+    assert sorted(rec) == ["fabhip_spline_packed_floats", "fabhip_spline_tape_layout"]
+    want = {tuple(r[:-1]): r[-1] for r in rec["fabhip_spline_packed_floats"]}
+    assert sorted(want) == sorted(shapes)
+    assert {s: lib.fabhip_spline_packed_floats(*s) for s in shapes} == want
+    cases = [s + (B,) for s, B in itertools.product(shapes, [1, 17, 2048])]
+    want = {tuple(r[:-1]): r[-1] for r in rec["fabhip_spline_tape_layout"]}
+    assert sorted(want) == sorted(cases), "the fixture does not hold the cases of this test"
+    lay = (C.c_int64 * 16)()
+    for c in cases:
+        assert lib.fabhip_spline_tape_layout(*c, lay) == 0
+        assert list(lay) == want[c], (c, list(lay), want[c])

@@ -80,11 +80,11 @@ def test_checker_pins_the_lowering_of_the_in_kernel_step_size_rule():
 
 # the kernels that must still be in the library, on the unit that holds them
 MUST_HOLD = {"ais_tile16": ("k_hmc_stepILi5E",), "ais_tile48": ("k_hmc_step_r4", "k_ais_init_r4", "k_hmc_step_r8", "k_ais_init_r8"),
-             "spline_kernels": ("k_spline_logprob_r8",)}
+             "spline_stream": ("k_spline_logprob_r8",), "spline_tile16": ("k_spline_logprobILi",)}
 
 
-@pytest.mark.parametrize("stem", ["flow_kernels", "ais_tile16", "ais_tile16_metropolis", "ais_tile48", "ais_moves", "spline_kernels",
-                                  "train_kernels"])
+@pytest.mark.parametrize("stem", ["flow_kernels", "ais_tile16", "ais_tile16_metropolis", "ais_tile48", "ais_moves", "spline_pack",
+                                  "spline_tile16", "spline_stream", "train_kernels"])
 def test_no_instruction_touches_a_register_whose_load_is_in_flight(stem):
     obj = os.path.join(BUILD, stem + ".o")
     if not os.path.exists(obj):

@@ -11,9 +11,10 @@ from fab_torch_amd import _isa_check as chk          # noqa: E402
 
 BUILD = os.path.join(ROOT, "fab_torch_amd", "build")
 AIS_OBJECTS = ("ais_tile16", "ais_tile16_metropolis", "ais_tile48", "ais_moves")       # (ais_driver holds no kernel)
-DEVICE_OBJECTS = ("flow_kernels",) + AIS_OBJECTS + ("spline_kernels", "train_kernels", "reduce_kernels", "resample_scan",
+SPLINE_OBJECTS = ("spline_pack", "spline_tile16", "spline_stream")
+DEVICE_OBJECTS = ("flow_kernels",) + AIS_OBJECTS + SPLINE_OBJECTS + ("train_kernels", "reduce_kernels", "resample_scan",
                                                     "resample_emit", "weight_decisions", "generic_kernels", "topk")
-ALIASES = {"spline": ("spline_kernels",), "flow": AIS_OBJECTS}
+ALIASES = {"spline": SPLINE_OBJECTS, "flow": AIS_OBJECTS}
 
 
 def main():
