@@ -95,6 +95,16 @@ class DefensiveArgs(C.Structure):       # fabhip_defensive_args
                 ("sel", C.c_void_p)]
 
 
+class FlowMoveArgs(C.Structure):       # fabhip_flow_move_args
+    _fields_ = [("flow", Flow), ("target", Target), ("point", Point), ("B", C.c_int64), ("n_valid", C.c_void_p),
+                ("cur", Anneal), ("noise_g", C.c_void_p), ("noise_h", C.c_void_p), ("p_accept", C.c_void_p),
+                ("n_accept", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class FlowMovesArgs(C.Structure):       # fabhip_flow_moves_args
+    _fields_ = [("n_moves", C.c_int32), ("noise_g", C.c_void_p), ("noise_h", C.c_void_p), ("p_accept_out", C.c_void_p)]
+
+
 # every symbol include/fabhip.h declares (checked by tests/test_cabi_and_host.py)
 SYMBOLS = [
     "fabhip_strerror", "fabhip_version", "fabhip_flow_packed_floats", "fabhip_flow_pack", "fabhip_flow_sample",
@@ -124,8 +134,10 @@ SYMBOLS = [
     "fabhip_ais_run_mix", "fabhip_ais_phase_mix", "fabhip_defensive_log_prob",
     "fabhip_resample_stratified_workspace_bytes", "fabhip_resample_stratified",
     "fabhip_next_beta", "fabhip_log_w_first",
+    "fabhip_flow_move_workspace_bytes", "fabhip_flow_move", "fabhip_ais_moves_workspace_bytes", "fabhip_ais_run_moves",
+    "fabhip_ais_phase_moves",
 ]
-ABI_VERSION = 224          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 225          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -159,6 +171,14 @@ def _declare(lib):
     lib.fabhip_ais_phase_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), i32, i32, i32, vp, vp]
     lib.fabhip_ais_run_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), vp]
     lib.fabhip_ais_phase_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_flow_move_workspace_bytes.restype = sz
+    lib.fabhip_flow_move_workspace_bytes.argtypes = [i64, i32]
+    lib.fabhip_flow_move.argtypes = [C.POINTER(FlowMoveArgs), vp]
+    lib.fabhip_ais_moves_workspace_bytes.restype = sz
+    lib.fabhip_ais_moves_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.fabhip_ais_run_moves.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), C.POINTER(FlowMovesArgs), vp]
+    lib.fabhip_ais_phase_moves.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), C.POINTER(FlowMovesArgs),
+                                           i32, i32, i32, vp, vp]
     lib.fabhip_defensive_log_prob.argtypes = [C.POINTER(Flow), C.POINTER(DefensiveArgs), vp, vp, vp, i64, vp, vp]
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]

@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 224          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 225          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC = 1, 2, 3
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -261,6 +261,25 @@ def _register_fakes():
     @rf("fabhip::next_beta")
     def _(log_w, log_q, log_p, n_valid, beta, alpha, p_target, rho, iters=24):
         return log_w.new_empty((4,), dtype=torch.float64)
+
+    @rf("fabhip::flow_move")
+    def _(packed, dim, n_layers, width, target_kind, target_params, locs, scales, x, log_q, log_p, grad_log_q, grad_log_p,
+          n_valid, beta, alpha, p_target, noise_g, noise_h, precision=0):
+        return x.new_empty((1,)), x.new_empty((1,), dtype=torch.int32)
+
+    @rf("fabhip::ais_run_moves")
+    def _(packed, dim, n_layers, width, target_kind, target_params, locs, scales, betas, alpha, p_target, transition, eps0,
+          noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first,
+          p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, tau, noise_r, want_trace, method, n_moves,
+          noise_g, noise_h):
+        B, D, M = eps0.shape[0], eps0.shape[1], len(betas) - 2
+        f = lambda *s: eps0.new_empty(s)                                           # noqa: E731
+        i = lambda *s: eps0.new_empty(s, dtype=torch.int32)                        # noqa: E731
+        hmc = transition == TRANSITION_HMC
+        smc, tr = tau is not None, tau is not None and want_trace
+        return [f(B, D), f(B), f(B), f(B, D) if hmc else f(0), f(B, D) if hmc else f(0), f(B), i(2), f(16),
+                f(B, D) if want_base else f(0), f(B) if want_base else f(0), i(M) if smc else i(0), f(M) if smc else f(0),
+                i(M, B) if tr else i(0), f(M, B) if tr else f(0), f(M, n_moves) if n_moves > 0 else f(0)]
 
     @rf("fabhip::resample_multinomial")
     def _(log_w, u):

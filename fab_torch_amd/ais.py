@@ -80,6 +80,24 @@ def _check_threshold(tau):
     return float(tau)
 
 
+def check_n_flow_moves(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 0:
+        raise _ops.FabhipError(f"n_flow_moves must be a non-negative integer: the flow-proposal moves in front of every "
+                               f"transition (got {k!r})")
+    return int(k)
+
+
+def check_move_noise(noise_g, noise_h, M: int, k: int, B: int, D: int):
+    """The draws of the flow-proposal moves: noise_g [M, k, B, D] normals (the proposals' base noise) and noise_h [M, k, B]
+    standard exponentials, float32."""
+    for name, t, shape in (("noise_g", noise_g, (M, k, B, D)), ("noise_h", noise_h, (M, k, B))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            got = (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__
+            raise _ops.FabhipError(f"{name} must be a float32 tensor of shape {list(shape)} "
+                                   f"([M, n_flow_moves, batch{', dim' if name == 'noise_g' else ''}]), got {got}")
+    return noise_g.contiguous(), noise_h.contiguous()
+
+
 def check_schedule(values, M: int, what: str = "distribution_spacing_type") -> torch.Tensor:
     """A caller's annealing schedule as the float64 `B_space` tensor: M + 2 finite, non-decreasing values from 0 to 1 (repeated
     entries are legal: the increment of such a step is skipped)."""
@@ -137,14 +155,22 @@ class AnnealedImportanceSampler:
     one offset per stratum (a hash of the transition's uniform and the stratum number; include/fabhip.h:
     fabhip_resample_stratified) instead of one for all of them - unbiased like the systematic scheme, but with a variance that is
     never above multinomial resampling's whatever the order of the chains.  The decision, `noise_r` and its draws are the same
-    for both; without `resample_threshold` the setting is inert."""
+    for both; without `resample_threshold` the setting is inert.
+
+    `n_flow_moves` (default 0: none): flow-proposal independence moves in front of every transition - step j runs [resampling
+    step,] n_flow_moves x (x' = a fresh sample of the flow, accepted with min(1, [pi_j(x') / q(x')] / [pi_j(x) / q(x)])), then
+    transition j: the one global move of the sampler (definition: tests/flow_move_spec.py; fabhip_flow_move).  The moves leave
+    pi_j invariant, so the weights are what they were; `last_flow_moves` holds the acceptance fractions [M, n_flow_moves] of the
+    last call (a device tensor).  RealNVP base and native target only."""
 
     def __init__(self, base_distribution, target_log_prob, transition_operator: TransitionOperator,
                  p_target: bool, alpha: Optional[float] = None, n_intermediate_distributions: int = 1,
                  distribution_spacing_type="linear", resample_threshold: Optional[float] = None,
-                 resample_method: str = "systematic", ess_decay: float = 0.7):
+                 resample_method: str = "systematic", ess_decay: float = 0.7, n_flow_moves: int = 0):
         if not p_target:
             assert alpha is not None, "Must specify alpha if AIS target is not p."
+        self.n_flow_moves = n_flow_moves
+        self.last_flow_moves = None       # float32 [M, n_flow_moves] on the device: acceptance fractions of the last call
         self.resample_threshold = resample_threshold
         self.resample_method = resample_method
         self.ess_decay = ess_decay        # adaptive schedules only: the fraction of the current ESS a step keeps
@@ -169,6 +195,30 @@ class AnnealedImportanceSampler:
     @resample_threshold.setter
     def resample_threshold(self, tau):
         self.__dict__["_resample_threshold"] = _check_threshold(tau)
+
+    @property
+    def n_flow_moves(self) -> int:
+        return self.__dict__.get("_n_flow_moves", 0)          # (0 for a sampler restored from a state that predates the setting)
+
+    @n_flow_moves.setter
+    def n_flow_moves(self, k):
+        self.__dict__["_n_flow_moves"] = check_n_flow_moves(k)
+
+    def _refuse_flow_moves(self, what: str):
+        if self.n_flow_moves > 0:
+            raise _ops.FabhipError(f"n_flow_moves={self.n_flow_moves} (flow-proposal moves) is not available for {what}: set "
+                                   "n_flow_moves=0, or use a RealNVP base distribution with a native target")
+
+    def _refuse_flow_move_routes(self):
+        """The routes the flow-proposal moves do not run on, refused by name before any op is reached."""
+        if self.n_flow_moves == 0:
+            return
+        if self._spline_parts() is not None:
+            self._refuse_flow_moves("the fused spline-flow call")
+        if isinstance(self.base_distribution, DefensiveMixtureDistribution):
+            self._refuse_flow_moves("a DefensiveMixtureDistribution base (the proposal would have to be the mixture)")
+        if not self.is_native:
+            self._refuse_flow_moves("the generic path (plug-in base distribution / target / transition operator)")
 
     @property
     def resample_method(self) -> str:
@@ -218,6 +268,8 @@ class AnnealedImportanceSampler:
             info.update(self._smc_info)                     # n_resampled, ess_min_in_chain of the last logged call
         if self.adaptive and self.__dict__.get("_adaptive_info") is not None:
             info.update(self._adaptive_info)                # beta_1, n_steps_to_beta_one, n_bisect_floor of the last call
+        if self.n_flow_moves > 0 and self.__dict__.get("_flow_move_info") is not None:
+            info.update(self._flow_move_info)               # flow_move_p_accept_dist0 / dist{M-1} of the last logged call
         info.update(self.transition_operator.get_logging_info())
         return info
 
@@ -276,6 +328,7 @@ class AnnealedImportanceSampler:
         uniform draws of the flow's base sample."""
         self._refuse_resampling("the fused spline-flow call")
         self._refuse_adaptive_routes()
+        self._refuse_flow_move_routes()
         flow, target = self._spline_parts()
         op = self.transition_operator
         head = self._call_head(flow, target, _ops.TRANSITION_HMC)[:-1]       # (HMC only: the spline op has no transition slot)
@@ -292,8 +345,11 @@ class AnnealedImportanceSampler:
         return Point(x, lq, lp, gq, gp), log_w, n_valid, stats, base_x, base_lw
 
     def run(self, batch_size: int, eps0=None, noise_a=None, noise_b=None, want_base: bool = False, u0=None, noise_r=None,
-            trace: bool = False, sel=None, force_betas=None):
-        """(`force_betas` [M + 2], adaptive schedules only: the call runs on this schedule; the decisions still run and are
+            trace: bool = False, sel=None, force_betas=None, noise_g=None, noise_h=None):
+        """(`noise_g` [M, k, B, D] normals / `noise_h` [M, k, B] standard exponentials, float32: the draws of the k =
+        n_flow_moves flow-proposal moves in front of every transition; absent: drawn on the device after noise_a / noise_b, g
+        before h.  An error with n_flow_moves == 0.)
+        (`force_betas` [M + 2], adaptive schedules only: the call runs on this schedule; the decisions still run and are
         recorded in `last_adaptive` - with `trace` together with the log_w, log_q, log_p each of them saw.)
         (`sel` [B] uniforms in [0, 1): the branch draws of a DefensiveMixtureDistribution base - chain i starts from the flow iff
         sel_i < sigmoid(mixture_logit); absent: drawn on the device after eps0 and before the transition noise.)
@@ -304,6 +360,12 @@ class AnnealedImportanceSampler:
         stats[16], base_x, base_log_w) without synchronising.  `want_base`: also return the chains' starting points
         after the "chain init" filtering and their log p - log q (generate_eval_data, ais.py:152-166)."""
         self._refuse_adaptive_routes()
+        self._refuse_flow_move_routes()
+        k_moves = self.n_flow_moves
+        if (noise_g is not None or noise_h is not None) and k_moves == 0:
+            raise _ops.FabhipError("noise_g / noise_h belong to the flow-proposal moves: set n_flow_moves first")
+        if (noise_g is None) != (noise_h is None):
+            raise _ops.FabhipError("pass both noise_g and noise_h (the draws of the flow-proposal moves) or neither")
         if force_betas is not None and not self.adaptive:
             raise _ops.FabhipError("force_betas belongs to distribution_spacing_type='adaptive'; a fixed schedule is passed as "
                                    "distribution_spacing_type itself")
@@ -314,7 +376,8 @@ class AnnealedImportanceSampler:
         if self.adaptive:
             if sel is not None:
                 raise _ops.FabhipError("sel (branch uniforms) belongs to a DefensiveMixtureDistribution base distribution")
-            return self._run_adaptive(batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas)
+            return self._run_adaptive(batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas, noise_g,
+                                      noise_h)
         ops = _ops.load()
         flow, target = self._native_parts()
         kind, slots = operator_slots(self.transition_operator)
@@ -338,6 +401,8 @@ class AnnealedImportanceSampler:
             if tau is None:
                 raise _ops.FabhipError("noise_r belongs to the SMC mode: set resample_threshold first")
             noise_r = check_noise_r(noise_r, M)
+        if noise_g is not None:
+            noise_g, noise_h = check_move_noise(noise_g, noise_h, M, k_moves, B, D)
         mix = self._mixture()
         if sel is not None:
             if mix is None:
@@ -352,6 +417,12 @@ class AnnealedImportanceSampler:
                                   noise_r, bool(trace), *mix.mix_args(), sel, True, RESAMPLE_METHODS[self.resample_method])
             if tau is None:
                 out = out[:10]
+        elif k_moves > 0:
+            # flow-proposal moves: the same call through ais_run_moves (plain and SMC mode; the acceptance fractions come last)
+            out = ops.ais_run_moves(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), tau, noise_r,
+                                    bool(trace), RESAMPLE_METHODS[self.resample_method], k_moves, noise_g, noise_h)
+            self.last_flow_moves = out[14]
+            out = out[:14] if tau is not None else out[:10]
         else:
             # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
             call = ops.ais_run if tau is None else ops.ais_run_smc
@@ -446,12 +517,14 @@ class AnnealedImportanceSampler:
                               _ops.precision_of(flow))
 
     # ---- adaptive schedule: the call stepped transition by transition, the next temperature chosen on the device ---------------
-    def _run_adaptive(self, batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas):
+    def _run_adaptive(self, batch_size, eps0, noise_a, noise_b, want_base, noise_r, trace, force_betas, noise_g=None,
+                      noise_h=None):
         """`run` with distribution_spacing_type="adaptive" (definition: tests/adaptive_spec.py).  FABHIP_AIS_INIT at beta_1 := 0,
         then per step: [resampling step +] transition j at beta_j through the phase op (betas[j] = betas[j + 1] = beta_j: no
         increment inside), fabhip_next_beta on the new point, ONE 32-byte read, the increment (fabhip_log_w_update: the fused
         kernels' expression; the first weight through fabhip_log_w_first: the chain initialisation's).  FABHIP_AIS_FINISH last.
-        Once beta has reached 1 the remaining transitions run on the target without a decision or an increment."""
+        Once beta has reached 1 the remaining transitions run on the target without a decision or an increment.
+        With n_flow_moves: fabhip::flow_move at beta_j between the resampling step and the transition of step j."""
         ops = _ops.load()
         flow, target = self._native_parts()
         kind, s = operator_slots(self.transition_operator)
@@ -471,15 +544,37 @@ class AnnealedImportanceSampler:
                    torch.zeros((M, B), dtype=torch.float32, device=dev) if trace else None)
             smc = (tau, noise_r, False, *rec, RESAMPLE_METHODS[self.resample_method])
         base = (torch.empty_like(st["x"]), torch.empty_like(st["log_w"])) if want_base else (None, None)
+        k_moves = self.n_flow_moves
+        if k_moves > 0:                                                          # (drawn behind noise_a / noise_b, g before h)
+            D = st["x"].shape[1]
+            if noise_g is None:
+                noise_g = torch.randn((M, k_moves, B, D), dtype=torch.float32, device=dev)
+                noise_h = torch.empty((M, k_moves, B), dtype=torch.float32, device=dev).exponential_(1.0)
+            else:
+                noise_g, noise_h = check_move_noise(noise_g, noise_h, M, k_moves, B, D)
+            fracs = []
 
-        def phase(phases, j0, j1, betas, base=(None, None)):
+        def phase(phases, j0, j1, betas, base=(None, None), part=None):
+            """(`part`: "resample" / "transition" runs that half of a step alone; None: the whole step)"""
             args = (*self._call_head(flow, target, kind, betas), phases, j0, j1, st["eps0"], st["noise_a"], st["noise_b"],
                     *s[:8], st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["log_w"], st["n_valid"], st["stats"], None,
                     *s[8:], *base, prec)
-            if smc and j0 <= j1:
-                ops.ais_phase_smc(*args, *smc)
+            if smc and j0 <= j1 and part != "transition":
+                ops.ais_phase_smc(*args, smc[0], smc[1], part == "resample", *smc[3:])
             else:
                 ops.ais_phase(*args)
+
+        def step(j, beta):
+            """Step j at beta: [resampling step,] [moves,] transition."""
+            if k_moves == 0:
+                return phase(0, j, j, at(j, beta))
+            if smc:
+                phase(0, j, j, at(j, beta), part="resample")
+            head = self._call_head(flow, target, kind)[:8]                       # (flow image, target)
+            for m in range(k_moves):
+                fracs.append(ops.flow_move(*head, st["x"], st["lq"], st["lp"], st["gq"], st["gp"], st["n_valid"], float(beta),
+                                           alpha, p_target, noise_g[j - 1, m], noise_h[j - 1, m], prec)[0])
+            phase(0, j, j, at(j, beta), part="transition")
 
         def at(j, beta):                         # the per-call betas of transition j: betas[j] = betas[j + 1] = beta
             b = [0.0] * (M + 2)
@@ -502,7 +597,7 @@ class AnnealedImportanceSampler:
             ops.log_w_first(st["lq"], st["lp"], chosen[1], alpha, p_target, st["log_w"])
         for j in range(1, M + 1):
             bj = chosen[j]
-            phase(0, j, j, at(j, bj))
+            step(j, bj)
             nxt = 1.0
             if j < M:
                 nxt = decide(j, bj) if bj < 1.0 else 1.0
@@ -517,6 +612,8 @@ class AnnealedImportanceSampler:
         self.__dict__["_adaptive_info"] = {
             "beta_1": float(chosen[1]), "n_steps_to_beta_one": int(next(i for i, b in enumerate(chosen) if b >= 1.0)),
             "n_bisect_floor": int(sum(d.floor for d in decisions))}
+        if k_moves > 0:
+            self.last_flow_moves = torch.cat(fracs).view(M, k_moves)
         if tau is not None:
             empty = torch.empty(0, device=dev)
             self.last_smc = (rec[0], rec[1], rec[2] if trace else empty.int(), rec[3] if trace else empty)
@@ -572,7 +669,8 @@ class AnnealedImportanceSampler:
 
     def perform_transition(self, x_new: Point, log_w: torch.Tensor, j: int):
         """ais.py:90-105: one MCMC transition towards the j-th intermediate distribution + the log-weight increment
-        (skipped when beta does not change).  The fused call does the same for all j inside `fabhip_ais_run`."""
+        (skipped when beta does not change).  The fused call does the same for all j inside `fabhip_ais_run`.
+        One LOCAL transition: `n_flow_moves` does not act here (the flow-proposal moves belong to the whole call)."""
         self._refuse_adaptive("perform_transition (one transition of a FIXED schedule)",
                               "run the whole call (sample_and_log_weights / run), or give the sampler a schedule of your own")
         beta, beta_next = float(self.B_space[j]), float(self.B_space[j + 1])
@@ -683,11 +781,24 @@ class AnnealedImportanceSampler:
             h = torch.stack([flag.float().sum(), ess.min()]).tolist()
             self.__dict__["_smc_info"] = {"n_resampled": int(h[0]), "ess_min_in_chain": float(h[1])}
 
+    def _log_flow_moves(self):
+        """flow_move_p_accept_dist0 / dist{M-1} of the call that just ended (moves on only): means over the k moves of the
+        first / last step; one more small read, after the call's own."""
+        self.__dict__["_flow_move_info"] = None
+        fm = self.last_flow_moves
+        if self.n_flow_moves > 0 and fm is not None and fm.numel() > 0:
+            M = fm.shape[0]
+            h = torch.stack([fm[0].mean(), fm[M - 1].mean()]).tolist()
+            self.__dict__["_flow_move_info"] = {"flow_move_p_accept_dist0": float(h[0]),
+                                                f"flow_move_p_accept_dist{M - 1}": float(h[1])}
+
     def sample_and_log_weights(self, batch_size: int, logging: bool = True, eps0=None, noise_a=None, noise_b=None,
-                               u0=None, noise_r=None, sel=None) -> Tuple[Point, torch.Tensor]:
+                               u0=None, noise_r=None, sel=None, noise_g=None, noise_h=None) -> Tuple[Point, torch.Tensor]:
         self._refuse_adaptive_routes()
+        self._refuse_flow_move_routes()
         fused_spline = self._spline_parts() is not None
-        smc_on = self.resample_threshold is not None or self.adaptive          # (both step outside the plain phase op's pieces)
+        # (SMC mode, adaptive schedules, flow-proposal moves: all step outside the plain phase op's pieces)
+        smc_on = self.resample_threshold is not None or self.adaptive or self.n_flow_moves > 0
         mix_on = self._mixture() is not None and self.is_native
         if sel is not None and not mix_on:
             raise _ops.FabhipError("sel (branch uniforms) belongs to the fused call over a DefensiveMixtureDistribution base")
@@ -724,7 +835,8 @@ class AnnealedImportanceSampler:
                 if smc_on:
                     self._pf_take(None)                                          # (a piece prefetched before the mode was set)
                     self.__dict__.pop("_pf_last_key", None)
-                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b, noise_r=noise_r, sel=sel)
+                point, log_w, n_valid, stats, _, _ = self.run(batch_size, eps0, noise_a, noise_b, noise_r=noise_r, sel=sel,
+                                                              noise_g=noise_g, noise_h=noise_h)
             host, (n_init, n_end) = _ops.read_counts_and_stats(n_valid, stats)   # the single device->host read
         if n_init == 0:
             raise NoValidPoints("init")
@@ -737,6 +849,7 @@ class AnnealedImportanceSampler:
         if logging:
             self._logging_info = LoggingInfo(ess_base=float(st[0]), ess_ais=float(st[3]), log_Z=float(st[4]))
             self._log_smc()
+            self._log_flow_moves()
         return point, log_w.detach()
 
     def generate_eval_data(self, outer_batch_size: int, inner_batch_size: int):

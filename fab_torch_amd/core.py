@@ -30,8 +30,9 @@ class FABModel:
     def __init__(self, flow, target_distribution, n_intermediate_distributions: int, alpha: float = 2.,
                  transition_operator: Optional[TransitionOperator] = None, ais_distribution_spacing: str = "linear",
                  loss_type: Optional[str] = None, use_ais: bool = True, ais_resample_threshold: Optional[float] = None,
-                 ais_resample_method: str = "systematic", ais_ess_decay: float = 0.7):
+                 ais_resample_method: str = "systematic", ais_ess_decay: float = 0.7, ais_n_flow_moves: int = 0):
         assert loss_type in SUPPORTED_LOSSES
+        self.ais_n_flow_moves = ais_n_flow_moves                   # flow-proposal moves in front of every transition (ais.py)
         self.ais_ess_decay = ais_ess_decay                         # adaptive schedules (ais_distribution_spacing="adaptive")
         self.ais_resample_threshold = ais_resample_threshold       # SMC mode of the sampler (ais.py), None: plain AIS
         self.ais_resample_method = check_resample_method(ais_resample_method)   # "systematic" / "stratified" ancestors of that mode
@@ -60,7 +61,7 @@ class FABModel:
             distribution_spacing_type=self.ais_distribution_spacing,
             resample_threshold=getattr(self, "ais_resample_threshold", None),
             resample_method=getattr(self, "ais_resample_method", "systematic"),
-            ess_decay=getattr(self, "ais_ess_decay", 0.7))
+            ess_decay=getattr(self, "ais_ess_decay", 0.7), n_flow_moves=getattr(self, "ais_n_flow_moves", 0))
 
     def parameters(self):
         return self.flow.parameters()

@@ -49,9 +49,16 @@ struct AisWs {
     unsigned long long* smc_cdf;       // [B]
     int *smc_anc, *smc_flag;           // [B], [1]
     float* smc_lw;                     // [1]
+    // flow-proposal moves, behind all of it; null without `moves`
+    unsigned long long* mv_word;       // the accept kernel's count word
+    float* mv_prop;                    // [B][3D+2] the proposal's Point
     size_t bytes;
 };
-static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, bool smc) {
+// the proposal's Point inside a [B][3D+2] buffer: x | grad log q | grad log p | log q | log p (gradients null when !with_grad)
+static PointDev prop_point(float* pb, long B, int D, bool with_grad) {
+    return PointDev{pb, pb + 3 * B * D, pb + 3 * B * D + B, with_grad ? pb + B * D : nullptr, with_grad ? pb + 2 * B * D : nullptr};
+}
+static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, bool smc, bool moves = false) {
     AisWs w{};
     size_t tws = fabhip_hmc_workspace_bytes(B, D, n_inner);
     const size_t mws = fabhip_metropolis_workspace_bytes(B, D, n_inner);
@@ -73,8 +80,39 @@ static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, bool smc)
         w.smc_flag = (int*)p;
         w.smc_lw = (float*)(p + 64);
     }
+    if (moves) {
+        w.mv_word = b.take<unsigned long long>(1);
+        w.mv_prop = b.take<float>((size_t)B * (3 * D + 2));
+    }
     w.bytes = (size_t)(b.p - (char*)workspace);
     return w;
+}
+
+struct FlowMoveWs {
+    unsigned long long* word;
+    float* prop;                       // [B][3D+2]
+    size_t bytes;
+};
+static FlowMoveWs carve_flow_move_ws(void* workspace, long B, int D) {
+    FlowMoveWs w;
+    Bump b{(char*)workspace, 256};
+    w.word = b.take<unsigned long long>(1);
+    w.prop = b.take<float>((size_t)B * (3 * D + 2));
+    w.bytes = (size_t)(b.p - (char*)workspace);
+    return w;
+}
+
+// One flow-proposal move (include/fabhip.h: fabhip_flow_move): sample, create_point, accept / commit.  `word` is zero.
+static int flow_move_impl(const fabhip_flow& flow, const fabhip_target& target, const fabhip_point& point, long B, const int* n_valid,
+                          fabhip_anneal c, const float* noise_g, const float* noise_h, float* p_accept, int* n_accept,
+                          unsigned long long* word, float* prop_buf, hipStream_t st) {
+    const int D = flow.dim;
+    const bool with_grad = point.grad_log_q != nullptr;
+    const PointDev pd = prop_point(prop_buf, B, D, with_grad);
+    const fabhip_point prop{pd.x, pd.lq, pd.lp, pd.gq, pd.gp};
+    FAB_TRY(fabhip_flow_sample(&flow, noise_g, prop.x, prop.log_q, B, (fabhip_stream_t)st));
+    FAB_TRY(fabhip_create_point(&flow, &target, &prop, with_grad ? 1 : 0, B, (fabhip_stream_t)st));
+    return flow_move_accept(point, pd, noise_h, n_valid, B, D, c, word, p_accept, n_accept, st);
 }
 
 struct SplineHmcWs {
@@ -425,6 +463,47 @@ int fabhip_ais_run_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, con
 
 int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix, int32_t phases,
                          int32_t j_begin, int32_t j_end, float* partials, fabhip_stream_t stream) {
+    return fabhip_ais_phase_moves(a, smc, mix, nullptr, phases, j_begin, j_end, partials, stream);
+}
+
+size_t fabhip_ais_moves_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, int32_t smc) {
+    return carve_ais_ws(nullptr, B, dim, n_inner, smc != 0, true).bytes;
+}
+
+int fabhip_ais_run_moves(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                         const fabhip_flow_moves_args* moves, fabhip_stream_t stream) {
+    if (!a) return FABHIP_EINVAL;
+    return fabhip_ais_phase_moves(a, smc, mix, moves, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+}
+
+size_t fabhip_flow_move_workspace_bytes(int64_t B, int32_t dim) {
+    if (B < 0 || dim < 1) return 0;
+    return carve_flow_move_ws(nullptr, B, dim).bytes;
+}
+
+int fabhip_flow_move(const fabhip_flow_move_args* a, fabhip_stream_t stream) {
+    if (!a || !a->flow.packed || !a->noise_g || !a->noise_h || !a->workspace || a->B < 0 || a->B > 0x3fffffffL) return FABHIP_EINVAL;
+    FAB_TRY(check_flow_shape(a->flow.dim, a->flow.n_layers, a->flow.width));
+    FAB_TRY(check_target(&a->target, a->flow.dim));
+    FAB_TRY(check_point(a->point, false));
+    if ((a->point.grad_log_q == nullptr) != (a->point.grad_log_p == nullptr)) return FABHIP_EINVAL;
+    if (((size_t)a->workspace & 255) != 0) return FABHIP_EINVAL;
+    const FlowMoveWs w = carve_flow_move_ws(a->workspace, a->B, a->flow.dim);
+    if (a->workspace_bytes < w.bytes) return FABHIP_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(w.word, 0, 8, st) != hipSuccess) return FABHIP_ELAUNCH;
+    if (a->B == 0) {                   // nothing to move: the outputs of an empty batch
+        if (a->p_accept && hipMemsetAsync(a->p_accept, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
+        if (a->n_accept && hipMemsetAsync(a->n_accept, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
+        return FABHIP_OK;
+    }
+    return flow_move_impl(a->flow, a->target, a->point, (long)a->B, a->n_valid, a->cur, a->noise_g, a->noise_h, a->p_accept,
+                          a->n_accept, w.word, w.prop, st);
+}
+
+int fabhip_ais_phase_moves(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                           const fabhip_flow_moves_args* moves, int32_t phases, int32_t j_begin, int32_t j_end, float* partials,
+                           fabhip_stream_t stream) {
     if (!a || !a->flow.packed || !a->betas || !a->step_state || !a->log_w ||
         !a->n_valid || !a->stats || !a->workspace || a->B < 1 || a->M < 1 || a->n_inner < 1)
         return FABHIP_EINVAL;
@@ -448,9 +527,16 @@ int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, c
     if (smc_on && partials) return FABHIP_ENOTSUP;
     if (smc_on && smc->method != FABHIP_SMC_SYSTEMATIC && smc->method != FABHIP_SMC_STRATIFIED) return FABHIP_EINVAL;
     if (smc_on && j_begin <= j_end && !smc->u) return FABHIP_EINVAL;                  // (like the noise: read by the transitions only)
-    const AisWs w = carve_ais_ws(a->workspace, a->B, a->flow.dim, a->n_inner, smc_on);
+    if (moves && moves->n_moves < 0) return FABHIP_EINVAL;
+    const bool mv_on = moves && moves->n_moves > 0;
+    if (mv_on && (partials || mx.on)) return FABHIP_ENOTSUP;                          // (sharded chains, defensive mixture)
+    if (mv_on && j_begin <= j_end && (!moves->noise_g || !moves->noise_h)) return FABHIP_EINVAL;
+    if (mv_on && a->B > 0x3fffffffL) return FABHIP_EINVAL;
+    const AisWs w = carve_ais_ws(a->workspace, a->B, a->flow.dim, a->n_inner, smc_on, mv_on);
     if (a->workspace_bytes < w.bytes) return FABHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
+    // (the accept kernel leaves its count word zero: one 8-byte fill per call that runs moves)
+    if (mv_on && j_begin <= j_end && hipMemsetAsync(w.mv_word, 0, 8, st) != hipSuccess) return FABHIP_ELAUNCH;
     const FlowDims f = flow_dims_of(a->flow);
     const TargetDev tg = make_target_dev(a->target);
     const int D = f.D;
@@ -518,6 +604,17 @@ int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, c
             FAB_TRY(smc_decide(k, st));
             FAB_TRY(smc_gather_copyback(a->point, a->log_w, w.tmp, w.smc_anc, w.smc_flag, w.smc_lw, a->n_valid, B, D, st));
             if (smc->only_resample) continue;
+        }
+        if (mv_on) {
+            // global moves of step j at beta_j, behind the resampling step and in front of the local transition: three launches
+            // each; they neither read nor write log_w, the step sizes or the ticket word
+            const int k = moves->n_moves;
+            for (int m = 0; m < k; ++m) {
+                const size_t slab = (size_t)(j - 1) * k + m;
+                FAB_TRY(flow_move_impl(a->flow, a->target, a->point, B, a->n_valid, cj, moves->noise_g + slab * B * D,
+                                       moves->noise_h + slab * B, moves->p_accept_out ? moves->p_accept_out + slab : nullptr,
+                                       nullptr, w.mv_word, w.mv_prop, st));
+            }
         }
         if (hmc) {
             fabhip_hmc_args h;

@@ -50,6 +50,9 @@ int compact_rows(const fabhip_point& point, float* log_w, long B, int dim, const
 // SMC mode: the point gathered by the ancestors `anc` through `tmp` and back (k_smc_gather, k_smc_copyback; both read `flag`)
 int smc_gather_copyback(const fabhip_point& point, float* log_w, float* tmp, const int* anc, const int* flag,
                         const float* lw_common, const int* n_ptr, long B, int dim, hipStream_t st);
+// flow-proposal move: accept / commit of the proposal's Point into `cur` (k_flow_move_accept; `word` is zero before and after)
+int flow_move_accept(const fabhip_point& cur, const PointDev& prop, const float* h, const int* n_ptr, long B, int dim,
+                     fabhip_anneal c, unsigned long long* word, float* p_accept, int* n_accept, hipStream_t st);
 // o = a - b over n floats (k_sub); the launch is not checked here
 void launch_sub(const float* a, const float* b, float* o, long n, hipStream_t st);
 // the spline family's initial log-weights (k_spline_init_logw); the launch is not checked here

@@ -268,7 +268,71 @@ __global__ __launch_bounds__(64 * SHARD_WAVES) void k_smc_shard_gather(SmcShardK
     }
 }
 
-__global__ void k_sub(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, long n) {
+// ------------------------------------------------------------------------------------------------
+// Flow-proposal independence move (include/fabhip.h: fabhip_flow_move; definition: tests/flow_move_spec.py): the accept /
+// commit step.  `prop` is the Point of a fresh flow sample; row i takes it iff it is live, both proposal densities are finite,
+// delta = r(prop) - r(cur) is a number and h_i > -delta, with r = pi_beta - log q in the expression order of
+// fabhip_anneal_log_prob.  16 lanes per row: lane 0 of the group decides, the group copies the row.  The count is an integer:
+// every workgroup adds (1 << 32 | its accepted rows) to ONE 64-bit word with a device-scope atomic, the workgroup that reads
+// gridDim.x - 1 finished workgroups in the returned value writes the outputs and zeroes the word for the next launch.
+// ------------------------------------------------------------------------------------------------
+constexpr int MOVE_LANES = 16;                       // lanes per row
+constexpr int MOVE_ROWS = 16;                        // rows per workgroup
+
+struct FlowMoveK {
+    PointDev cur;          // in / out
+    PointDev prop;         // the proposal's Point (gq / gp null with a gradient-free operator)
+    const float* h;        // [B] ~ Exp(1)
+    const int* n_ptr;      // rows in use (device; null: B)
+    long B;
+    int D;
+    fabhip_anneal c;       // beta_j
+    unsigned long long* word;   // zero before the launch; zero again after it
+    float* p_accept_out;   // optional [1]: n_accept / n_valid
+    int* n_accept_out;     // optional [1]
+};
+
+__device__ __forceinline__ float move_ratio(const fabhip_anneal& c, float lq, float lp) { return (c.c_q * lq + c.c_p * lp) - lq; }
+
+__global__ __launch_bounds__(MOVE_LANES * MOVE_ROWS) void k_flow_move_accept(FlowMoveK a) {
+    __shared__ int wave_n[MOVE_LANES * MOVE_ROWS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, sub = tid & (MOVE_LANES - 1);
+    long n0 = a.n_ptr ? (long)*a.n_ptr : a.B;
+    n0 = n0 < 0 ? 0 : (n0 > a.B ? a.B : n0);
+    const long r = (long)blockIdx.x * MOVE_ROWS + tid / MOVE_LANES;
+    int acc = 0;
+    if (sub == 0 && r < n0) {
+        const float lqn = a.prop.lq[r], lpn = a.prop.lp[r];
+        const float delta = move_ratio(a.c, lqn, lpn) - move_ratio(a.c, a.cur.lq[r], a.cur.lp[r]);
+        acc = (isfinite(lqn) && isfinite(lpn) && delta == delta && a.h[r] > -delta) ? 1 : 0;
+    }
+    const unsigned long long bal = __ballot(acc != 0);           // (one bit per accepted row: only lane 0 of a group can set it)
+    acc = __shfl(acc, lane & ~(MOVE_LANES - 1));                 // the group's decision
+    if (acc) {
+        const int D = a.D;
+        for (int j = sub; j < D; j += MOVE_LANES) {
+            a.cur.x[r * D + j] = a.prop.x[r * D + j];
+            if (a.cur.gq) { a.cur.gq[r * D + j] = a.prop.gq[r * D + j]; a.cur.gp[r * D + j] = a.prop.gp[r * D + j]; }
+        }
+        if (sub == 0) { a.cur.lq[r] = a.prop.lq[r]; a.cur.lp[r] = a.prop.lp[r]; }
+    }
+    if (lane == 0) wave_n[tid >> 6] = __popcll(bal);
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+        for (int i = 0; i < MOVE_LANES * MOVE_ROWS / 64; ++i) n += wave_n[i];
+        const unsigned long long old = __hip_atomic_fetch_add(a.word, (1ull << 32) | (unsigned long long)n, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(old >> 32) == gridDim.x - 1) {            // the last workgroup: every other one's rows are in `old`
+            const int total = (int)(unsigned)(old & 0xffffffffull) + n;
+            if (a.n_accept_out) *a.n_accept_out = total;
+            if (a.p_accept_out) *a.p_accept_out = n0 > 0 ? (float)total / (float)n0 : 0.f;
+            __hip_atomic_store(a.word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+__global__ void k_sub(const float* __restrict__ a,const float* __restrict__ b, float* __restrict__ o, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = a[i] - b[i];
 }
 
@@ -305,6 +369,15 @@ int smc_gather_copyback(const fabhip_point& point, float* log_w, float* tmp, con
     const int grid = (int)(B < 4096 ? B : 4096);
     hipLaunchKernelGGL(k_smc_gather, dim3(grid), dim3(64), 0, st, g);
     hipLaunchKernelGGL(k_smc_copyback, dim3(grid), dim3(64), 0, st, g);
+    return check_launch();
+}
+
+int flow_move_accept(const fabhip_point& cur, const PointDev& prop, const float* h, const int* n_ptr, long B, int dim,
+                     fabhip_anneal c, unsigned long long* word, float* p_accept, int* n_accept, hipStream_t st) {
+    FlowMoveK k{make_point_dev(cur), prop, h, n_ptr, B, dim, c, word, p_accept, n_accept};
+    const long grid = (B + MOVE_ROWS - 1) / MOVE_ROWS;
+    if (grid < 1 || grid > 0x7fffffffL) return FABHIP_EINVAL;
+    hipLaunchKernelGGL(k_flow_move_accept, dim3((unsigned)grid), dim3(MOVE_LANES * MOVE_ROWS), 0, st, k);
     return check_launch();
 }
 

@@ -912,7 +912,7 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
                    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune,
                    const optional<Tensor>& p_accept_first, const optional<Tensor>& p_accept_last,
                    const optional<Tensor>& avg_distance_first, const optional<Tensor>& avg_distance_last, int64_t precision,
-                   bool smc_on) {
+                   bool smc_on, bool moves_on = false) {
     fabhip_ais_args& a = c.a;
     a.flow = make_flow(packed, dim, n_layers, width, precision);
     a.target = make_target(kind, prm, locs, scales, dim, packed);
@@ -934,8 +934,9 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
     a.n_inner = (int32_t)n_inner; a.L = (int32_t)L; a.max_grad = (float)max_grad;
     a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
     fill_logging_slots(a, n_inner, ref, p_accept_first, p_accept_last, avg_distance_first, avg_distance_last);
-    const size_t nb = smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
-                             : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
+    const size_t nb = moves_on ? fabhip_ais_moves_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner, smc_on ? 1 : 0)
+                      : smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
+                               : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
     c.ws = scratch(nb, ref);
     a.workspace = aligned(c.ws); a.workspace_bytes = nb;
 }
@@ -947,6 +948,13 @@ struct MixOp {
     Tensor loc, log_scale, logit;
     optional<Tensor> sel;
 };
+// Flow-proposal moves of the AIS ops (fabhip_flow_moves_args): n_moves moves in front of every transition.  noise_g [M, k, B, dim]
+// / noise_h [M, k, B] absent: drawn from the default generator AFTER the transition noise, g before h (and before noise_r).
+struct MovesOp {
+    int64_t n_moves = 0;
+    optional<Tensor> noise_g, noise_h;
+    Tensor g, h, p_accept;                              // the draws the call used; out: acceptance fractions [M, k]
+};
 // SMC mode of the AIS ops (fabhip_smc_args): `tau` absent = the plain call through the same entry points.  noise_r [M] float64
 // (absent: drawn from the default generator AFTER the transition noise); the per-transition records are allocated here.
 struct SmcOp {
@@ -956,6 +964,7 @@ struct SmcOp {
     int64_t method = 0;                                 // FABHIP_SMC_SYSTEMATIC / FABHIP_SMC_STRATIFIED
     Tensor resampled, ess, ancestors, log_w_pre, u;     // out (ais_run_smc)
     const MixOp* mix = nullptr;                         // ais_run_mix: the call goes through fabhip_ais_*_mix
+    MovesOp* moves = nullptr;                           // ais_run_moves: the call goes through fabhip_ais_*_moves
 };
 
 fabhip_defensive_args make_mix(const MixOp& m, int64_t dim, const Tensor& ref) {
@@ -997,10 +1006,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     TORCH_CHECK(noise_a_in.has_value() == noise_b_in.has_value(), "fabhip: pass both noise tensors or neither");
     const bool draw_inside = !noise_a_in.has_value();
     TORCH_CHECK(eps0.dim() == 2 && eps0.size(1) == dim, "fabhip: eps0 must be [B, dim]");
+    MovesOp* mv = smc != nullptr ? smc->moves : nullptr;
+    TORCH_CHECK(mv == nullptr || mv->n_moves >= 0, "fabhip: n_moves must be >= 0");
+    const bool moves_on = mv != nullptr && mv->n_moves > 0;
     AisCall c;
     fill_ais_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0.size(0), eps0,
                   step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first, p_accept_last,
-                  avg_distance_first, avg_distance_last, precision, smc_on);
+                  avg_distance_first, avg_distance_last, precision, smc_on, moves_on);
     fabhip_ais_args& a = c.a;
     const int64_t B = c.B, M = c.M;
     const bool hmc = c.hmc;
@@ -1041,6 +1053,19 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
         }
     };
     const fabhip_smc_args* sap = smc != nullptr ? &sa : nullptr;
+    fabhip_flow_moves_args fm = {};
+    auto moves_noise = [&]() {                                 // (behind the transition noise, in front of noise_r)
+        if (!moves_on) return;
+        const int64_t k = mv->n_moves;
+        TORCH_CHECK(mv->noise_g.has_value() == mv->noise_h.has_value(), "fabhip: pass both noise_g and noise_h or neither");
+        mv->g = mv->noise_g.has_value() ? *mv->noise_g : at::randn({M, k, B, dim}, eps0.options());
+        mv->h = mv->noise_h.has_value() ? *mv->noise_h : at::empty({M, k, B}, eps0.options()).exponential_(1.0);
+        mv->p_accept = fempty({M, k}, eps0);
+        fm.n_moves = (int32_t)k;
+        fm.noise_g = fpn(mv->g, M * k * B * dim, eps0, "noise_g"); fm.noise_h = fpn(mv->h, M * k * B, eps0, "noise_h");
+        fm.p_accept_out = mv->p_accept.data_ptr<float>();
+    };
+    const fabhip_flow_moves_args* fmp = moves_on ? &fm : nullptr;
     const fabhip_stream_t st = stream_of(eps0);
     // defensive mixture (ais_run_mix): the same entry points with a non-NULL fabhip_defensive_args; `sel` absent: drawn after eps0
     // (the caller's draw) and before the transition noise
@@ -1057,16 +1082,18 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     }
     const char* what = map ? "ais_run_mix" : "ais_run";
     if (!draw_inside) {
+        moves_noise();
         smc_outputs();
-        chk(fabhip_ais_run_mix(&a, sap, map, st), what);
+        chk(fabhip_ais_run_moves(&a, sap, map, fmp, st), what);
     } else {
-        chk(fabhip_ais_phase_mix(&a, sap, map, FABHIP_AIS_INIT, 1, 0, nullptr, st),
+        chk(fabhip_ais_phase_moves(&a, sap, map, nullptr, FABHIP_AIS_INIT, 1, 0, nullptr, st),
             map ? "ais_run_mix (chain initialisation)" : "ais_run (chain initialisation)");
         noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
         noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
         a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
+        moves_noise();
         smc_outputs();
-        chk(fabhip_ais_phase_mix(&a, sap, map, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
+        chk(fabhip_ais_phase_moves(&a, sap, map, fmp, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
             map ? "ais_run_mix (transitions)" : "ais_run (transitions)");
     }
     return {x, lq, lp, gq, gp, log_w, o.n_valid, o.stats, o.base_x, o.base_lw};
@@ -1091,6 +1118,65 @@ std::vector<Tensor> ais_run_smc(
     return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
             std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
             e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
+}
+
+// ais_run_smc with n_moves flow-proposal moves in front of every transition (fabhip_ais_run_moves; `tau` absent: plain AIS with
+// moves): the fourteen outputs of ais_run_smc, then the acceptance fractions float[M, n_moves] (empty with n_moves == 0, which
+// is ais_run_smc launch for launch).
+std::vector<Tensor> ais_run_moves(
+    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
+    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
+    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
+    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
+    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, int64_t method, int64_t n_moves,
+    const optional<Tensor>& noise_g, const optional<Tensor>& noise_h) {
+    MovesOp mv;
+    mv.n_moves = n_moves; mv.noise_g = noise_g; mv.noise_h = noise_h;
+    SmcOp smc;
+    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.method = method; smc.moves = &mv;
+    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
+    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
+    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
+            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
+            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat), e(mv.p_accept, at::kFloat)};
+}
+
+// One flow-proposal independence move on Point tensors, in place (fabhip_flow_move): (acceptance fraction float[1], accepted
+// rows int32[1]).  grad_log_q / grad_log_p absent: a gradient-free operator's point.  n_valid (int32, device): rows in use.
+std::tuple<Tensor, Tensor> flow_move(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
+                                     at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales, Tensor x,
+                                     Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q, optional<Tensor> grad_log_p,
+                                     const optional<Tensor>& n_valid, double beta, double alpha, bool p_target,
+                                     const Tensor& noise_g, const Tensor& noise_h, int64_t precision) {
+    c10::DeviceGuard g(x.device());
+    fabhip_flow_move_args a = {};
+    a.flow = make_flow(packed, dim, n_layers, width, precision);
+    a.target = make_target(kind, prm, locs, scales, dim, packed);
+    TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
+    TORCH_CHECK(grad_log_q.has_value() == grad_log_p.has_value(), "fabhip: pass both gradient fields of the Point or neither");
+    const int64_t B = x.size(0);
+    const bool wg = grad_log_q.has_value();
+    a.point = fabhip_point{fpm(x, "x"), fpmn(log_q, B, x, "log_q"), fpmn(log_p, B, x, "log_p"),
+                           wg ? fpmn(*grad_log_q, B * dim, x, "grad_log_q") : nullptr,
+                           wg ? fpmn(*grad_log_p, B * dim, x, "grad_log_p") : nullptr};
+    a.B = B;
+    if (n_valid.has_value()) {
+        need(*n_valid, at::kInt, "n_valid"); need_n(*n_valid, 1, x, "n_valid", true);
+        a.n_valid = n_valid->data_ptr<int32_t>();
+    }
+    a.cur = coefs(beta, alpha, p_target);
+    a.noise_g = fpn(noise_g, B * dim, x, "noise_g"); a.noise_h = fpn(noise_h, B, x, "noise_h");
+    Tensor frac = fempty({1}, x), count = at::empty({1}, x.options().dtype(at::kInt));
+    a.p_accept = frac.data_ptr<float>(); a.n_accept = count.data_ptr<int32_t>();
+    const size_t nb = fabhip_flow_move_workspace_bytes(B, (int32_t)dim);
+    Tensor ws = scratch(nb, x);
+    a.workspace = aligned(ws); a.workspace_bytes = nb;
+    chk(fabhip_flow_move(&a, stream_of(x)), "flow_move");
+    return {frac, count};
 }
 
 // ais_run_smc with the defensive mixture as base distribution (fabhip_ais_run_mix): the fourteen outputs of ais_run_smc.
@@ -1668,6 +1754,14 @@ TORCH_LIBRARY(fabhip, m) {
           "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
           "Tensor? noise_r, bool want_trace, Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor? sel, "
           "bool enabled=True, int method=0) -> Tensor[]");
+    m.def("ais_run_moves(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
+          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
+          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
+          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
+          "Tensor? noise_r, bool want_trace, int method, int n_moves, Tensor? noise_g, Tensor? noise_h) -> Tensor[]");
+    m.def("flow_move(" FLW ", " TGT ", Tensor(a!) x, Tensor(b!) log_q, Tensor(c!) log_p, Tensor(d!)? grad_log_q, "
+          "Tensor(e!)? grad_log_p, Tensor? n_valid, float beta, float alpha, bool p_target, Tensor noise_g, Tensor noise_h, "
+          "int precision=0) -> (Tensor, Tensor)");
     m.def("defensive_log_prob(" FLW ", Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor x, bool with_grad, "
           "int precision=0) -> (Tensor, Tensor)");
     m.def("ais_phase_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
@@ -1769,6 +1863,8 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("ais_run_smc", ais_run_smc);
     m.impl("ais_phase_smc", ais_phase_smc);
     m.impl("ais_run_mix", ais_run_mix);
+    m.impl("ais_run_moves", ais_run_moves);
+    m.impl("flow_move", flow_move);
     m.impl("defensive_log_prob", defensive_log_prob);
     m.impl("smc_decide", smc_decide);
     m.impl("next_beta", next_beta);

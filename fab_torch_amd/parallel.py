@@ -137,6 +137,16 @@ def refuse_adaptive(who: str, sampler):
                           "distribution_spacing_type to 'linear', 'geometric' or a schedule of your own on the sampler")
 
 
+def refuse_flow_moves(who: str, sampler):
+    """A flow-proposal move's acceptance fraction and the fused call's moves have no `partials` form (fabhip_ais_phase_moves
+    returns FABHIP_ENOTSUP with sharded chains): the sharded samplers refuse a sampler with `n_flow_moves` set."""
+    k = getattr(sampler, "n_flow_moves", 0)
+    if k:
+        from ._ops import FabhipError
+        raise FabhipError(f"{who}: n_flow_moves={k} (flow-proposal moves) is not available for sharded chains; set "
+                          "n_flow_moves=0 on the sampler, or run the moves on one device (AnnealedImportanceSampler)")
+
+
 def refuse_mixture(who: str, sampler):
     """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_run_mix has no `partials` form and
     the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
@@ -167,6 +177,7 @@ class ShardedAIS:
         refuse_resampling("ShardedAIS", getattr(getattr(self.local_sampler, "__self__", None), "resample_threshold", None))
         refuse_mixture("ShardedAIS", getattr(self.local_sampler, "__self__", None))
         refuse_adaptive("ShardedAIS", getattr(self.local_sampler, "__self__", None))
+        refuse_flow_moves("ShardedAIS", getattr(self.local_sampler, "__self__", None))
         x, log_w, log_q = self.local_sampler(sizes[rank])
         if self.sync_step_size and self.step_state is not None and world > 1:
             # ONE tiny all-reduce for all step-size tensors (epsilons [M, n_outer] + common_epsilon [1]: latency-bound)
@@ -445,6 +456,7 @@ class ShardedAnnealedImportanceSampler:
         tau = getattr(getattr(be, "ais", None), "resample_threshold", None)
         smc_on = self.resample_across_ranks and tau is not None
         refuse_adaptive("ShardedAnnealedImportanceSampler", getattr(be, "ais", None))
+        refuse_flow_moves("ShardedAnnealedImportanceSampler", getattr(be, "ais", None))
         if not self.resample_across_ranks:
             refuse_resampling("ShardedAnnealedImportanceSampler", tau)
         else:

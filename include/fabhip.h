@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 224
+#define FABHIP_ABI_VERSION 225
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -680,6 +680,53 @@ int fabhip_ais_phase_mix(const fabhip_ais_args* args, const fabhip_smc_args* smc
  * operators stepped from the host.  `mix->sel` is not read.  `workspace`: reserved, may be NULL. */
 int fabhip_defensive_log_prob(const fabhip_flow* flow, const fabhip_defensive_args* mix, const float* x, float* log_q,
                               float* grad_x, int64_t B, void* workspace, fabhip_stream_t stream);
+
+/* Flow-proposal independence move (ABI 225; definition: tests/flow_move_spec.py).  One move at beta (coefficients `cur`):
+ * x' = a fresh sample of the flow from noise_g, (x', lq', lp'[, gq', gp']) its Point, and with
+ *     r(lq, lp) = (c_q lq + c_p lp) - lq       (float32, un-fused, the expression order of fabhip_anneal_log_prob)
+ *     delta_i   = r(lq'_i, lp'_i) - r(lq_i, lp_i)
+ * row i < n_valid takes the proposal's fields iff lq'_i and lp'_i are finite, delta_i is a number and noise_h_i > -delta_i
+ * (noise_h ~ Exp(1): the Metropolis-Hastings test of an independence sampler without exp or log).  Every other row - the rows
+ * at and beyond n_valid among them - is left as it is.  The move leaves pi_beta invariant: log-weights are not touched.
+ * Three launches: fabhip_flow_sample into the workspace, fabhip_create_point on the proposals (gradients iff the point has
+ * them; the flow's `precision` as given), the accept / commit kernel.  No host read.  n_accept [1] (int32) and p_accept [1]
+ * = float32(n_accept) / float32(n_valid) (0 with n_valid == 0) may each be NULL.  workspace: 256-byte aligned,
+ * fabhip_flow_move_workspace_bytes(B, dim). */
+typedef struct {
+    fabhip_flow flow;
+    fabhip_target target;
+    fabhip_point point;       /* in/out; grad_log_q / grad_log_p both NULL: a gradient-free operator's point */
+    int64_t B;
+    const int32_t* n_valid;   /* device scalar: rows in use (NULL -> B) */
+    fabhip_anneal cur;        /* beta */
+    const float* noise_g;     /* [B][dim] ~ N(0,1): the flow's base noise */
+    const float* noise_h;     /* [B] ~ Exp(1) */
+    float* p_accept;          /* [1] out or NULL */
+    int32_t* n_accept;        /* [1] out or NULL */
+    void* workspace;
+    size_t workspace_bytes;
+} fabhip_flow_move_args;
+size_t fabhip_flow_move_workspace_bytes(int64_t B, int32_t dim);
+int fabhip_flow_move(const fabhip_flow_move_args* args, fabhip_stream_t stream);
+
+/* The moves inside the fused call: step j = 1 .. M runs [resampling step,] n_moves moves at beta_j, then transition j
+ * (resample, move globally, move locally).  Steps run with smc->only_resample skip the moves.  noise_g / noise_h are read by
+ * the transitions only (like noise_a / noise_b); with n_moves > 0 and transitions to run, NULL is FABHIP_EINVAL.  n_moves == 0
+ * (or a NULL fabhip_flow_moves_args): the call without moves, launch for launch.  With `partials` (sharded chains) or a
+ * defensive mixture: FABHIP_ENOTSUP.  Workspace: fabhip_ais_moves_workspace_bytes (smc != 0: with the resampling step's
+ * share), the layout of the call without moves with the proposal buffers behind it. */
+typedef struct {
+    int32_t n_moves;          /* k >= 0 */
+    const float* noise_g;     /* device [M][k][B][dim] ~ N(0,1) */
+    const float* noise_h;     /* device [M][k][B] ~ Exp(1) */
+    float* p_accept_out;      /* device [M][k] acceptance fractions, or NULL; entry (j - 1, m) is written by step j's phase */
+} fabhip_flow_moves_args;
+size_t fabhip_ais_moves_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, int32_t smc);
+int fabhip_ais_run_moves(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                         const fabhip_flow_moves_args* moves, fabhip_stream_t stream);
+int fabhip_ais_phase_moves(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
+                           const fabhip_flow_moves_args* moves, int32_t phases, int32_t j_begin, int32_t j_end,
+                           float* partials, fabhip_stream_t stream);
 
 /* The decision alone, for samplers that step their transitions themselves (the generic plug-in path): ancestors [B] (identity
  * where nothing is resampled and beyond *n_ptr rows), resampled [1], log_w_common [1] (the value every log_w[:n0] takes when
