@@ -105,6 +105,10 @@ class FlowMovesArgs(C.Structure):       # fabhip_flow_moves_args
     _fields_ = [("n_moves", C.c_int32), ("noise_g", C.c_void_p), ("noise_h", C.c_void_p), ("p_accept_out", C.c_void_p)]
 
 
+class AisExt(C.Structure):       # fabhip_ais_ext: the optional modes of the fused call, each NULL or a pointer to its struct
+    _fields_ = [("smc", C.POINTER(SmcArgs)), ("mix", C.POINTER(DefensiveArgs)), ("moves", C.POINTER(FlowMovesArgs))]
+
+
 # every symbol include/fabhip.h declares (checked by tests/test_cabi_and_host.py)
 SYMBOLS = [
     "fabhip_strerror", "fabhip_version", "fabhip_flow_packed_floats", "fabhip_flow_pack", "fabhip_flow_sample",
@@ -128,16 +132,15 @@ SYMBOLS = [
     "fabhip_metropolis_partials_floats", "fabhip_metropolis_adapt_gathered",
     "fabhip_flow_pack_train", "fabhip_flow_log_prob_tape_rows", "fabhip_train_step_workspace_bytes", "fabhip_buffer_train_step",
     "fabhip_buffer_add", "fabhip_buffer_sample_workspace_bytes", "fabhip_buffer_sample",
-    "fabhip_ais_smc_workspace_bytes", "fabhip_ais_run_smc", "fabhip_ais_phase_smc", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
+    "fabhip_ais_ext_workspace_bytes", "fabhip_ais_run_ext", "fabhip_ais_phase_ext", "fabhip_smc_workspace_bytes", "fabhip_smc_decide",
     "fabhip_train_step_plan", "fabhip_resample_stream_workspace_bytes", "fabhip_resample_multinomial_stream",
     "fabhip_smc_shard_workspace_bytes", "fabhip_smc_shard_pack", "fabhip_smc_shard_resample",
-    "fabhip_ais_run_mix", "fabhip_ais_phase_mix", "fabhip_defensive_log_prob",
+    "fabhip_defensive_log_prob",
     "fabhip_resample_stratified_workspace_bytes", "fabhip_resample_stratified",
     "fabhip_next_beta", "fabhip_log_w_first",
-    "fabhip_flow_move_workspace_bytes", "fabhip_flow_move", "fabhip_ais_moves_workspace_bytes", "fabhip_ais_run_moves",
-    "fabhip_ais_phase_moves",
+    "fabhip_flow_move_workspace_bytes", "fabhip_flow_move",
 ]
-ABI_VERSION = 225          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 226          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):
@@ -165,20 +168,13 @@ def _declare(lib):
     lib.fabhip_ais_workspace_bytes.argtypes = [i64, i32, i32]
     lib.fabhip_ais_run.argtypes = [C.POINTER(AisArgs), vp]
     lib.fabhip_ais_phase.argtypes = [C.POINTER(AisArgs), i32, i32, i32, vp, vp]
-    lib.fabhip_ais_smc_workspace_bytes.restype = sz
-    lib.fabhip_ais_smc_workspace_bytes.argtypes = [i64, i32, i32]
-    lib.fabhip_ais_run_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), vp]
-    lib.fabhip_ais_phase_smc.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), i32, i32, i32, vp, vp]
-    lib.fabhip_ais_run_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), vp]
-    lib.fabhip_ais_phase_mix.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), i32, i32, i32, vp, vp]
+    lib.fabhip_ais_ext_workspace_bytes.restype = sz
+    lib.fabhip_ais_ext_workspace_bytes.argtypes = [i64, i32, i32, C.POINTER(AisExt)]
+    lib.fabhip_ais_run_ext.argtypes = [C.POINTER(AisArgs), C.POINTER(AisExt), vp]
+    lib.fabhip_ais_phase_ext.argtypes = [C.POINTER(AisArgs), C.POINTER(AisExt), i32, i32, i32, vp, vp]
     lib.fabhip_flow_move_workspace_bytes.restype = sz
     lib.fabhip_flow_move_workspace_bytes.argtypes = [i64, i32]
     lib.fabhip_flow_move.argtypes = [C.POINTER(FlowMoveArgs), vp]
-    lib.fabhip_ais_moves_workspace_bytes.restype = sz
-    lib.fabhip_ais_moves_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.fabhip_ais_run_moves.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), C.POINTER(FlowMovesArgs), vp]
-    lib.fabhip_ais_phase_moves.argtypes = [C.POINTER(AisArgs), C.POINTER(SmcArgs), C.POINTER(DefensiveArgs), C.POINTER(FlowMovesArgs),
-                                           i32, i32, i32, vp, vp]
     lib.fabhip_defensive_log_prob.argtypes = [C.POINTER(Flow), C.POINTER(DefensiveArgs), vp, vp, vp, i64, vp, vp]
     lib.fabhip_smc_workspace_bytes.restype = sz
     lib.fabhip_smc_workspace_bytes.argtypes = [i64]

@@ -14,7 +14,7 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 225          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 226          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
 TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC = 1, 2, 3
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
@@ -267,11 +267,12 @@ def _register_fakes():
           n_valid, beta, alpha, p_target, noise_g, noise_h, precision=0):
         return x.new_empty((1,)), x.new_empty((1,), dtype=torch.int32)
 
-    @rf("fabhip::ais_run_moves")
+    @rf("fabhip::ais_run_ext")
     def _(packed, dim, n_layers, width, target_kind, target_params, locs, scales, betas, alpha, p_target, transition, eps0,
           noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first,
-          p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, tau, noise_r, want_trace, method, n_moves,
-          noise_g, noise_h):
+          p_accept_last, avg_distance_first, avg_distance_last, want_base, precision, tau=None, noise_r=None, want_trace=False,
+          method=0, mix_loc=None, mix_log_scale=None, mix_logit=None, sel=None, mix_enabled=False, n_moves=0, noise_g=None,
+          noise_h=None):
         B, D, M = eps0.shape[0], eps0.shape[1], len(betas) - 2
         f = lambda *s: eps0.new_empty(s)                                           # noqa: E731
         i = lambda *s: eps0.new_empty(s, dtype=torch.int32)                        # noqa: E731

@@ -44,7 +44,7 @@ def check_noise_r(noise_r: torch.Tensor, M: int) -> torch.Tensor:
     return noise_r.contiguous()
 
 
-# The transition operator's segment of the fused ops' argument lists, in schema order (ais_run / ais_run_smc / spline_ais_run
+# The transition operator's segment of the fused ops' argument lists, in schema order (ais_run / ais_run_ext / spline_ais_run
 # take it whole; ais_phase takes the four logging slots apart, behind the state tensors).
 OperatorSlots = namedtuple("OperatorSlots", "step_state common_epsilon mass n_inner L max_grad target_p_accept tune "
                                             "p_accept_first p_accept_last avg_distance_first avg_distance_last")
@@ -299,11 +299,11 @@ class AnnealedImportanceSampler:
     def _refuse_mixture(self, what: str):
         if self._mixture() is not None:
             raise _ops.FabhipError(f"a DefensiveMixtureDistribution base is not available for {what}: the mixture runs through "
-                                   "the one-op fused call (fabhip::ais_run_mix) only")
+                                   "the one-op fused call (fabhip::ais_run_ext) only")
 
     def _native_parts(self) -> Tuple[RealNVP, _NativeTarget]:
         """(RealNVP, native target) of the fused call; with a defensive mixture as base distribution the RealNVP inside it
-        (`_mixture()` tells the two apart: the mixture's call is ais_run_mix)."""
+        (`_mixture()` tells the two apart: the mixture's call is ais_run_ext with its mix group)."""
         mix = self._mixture()
         flow = mix.flow if mix is not None else self.base_distribution
         if not isinstance(flow, RealNVP):
@@ -410,28 +410,22 @@ class AnnealedImportanceSampler:
             if not torch.is_tensor(sel) or sel.dtype != torch.float32 or tuple(sel.shape) != (B,):
                 raise _ops.FabhipError(f"sel must be a float32 tensor of shape [{B}] (one uniform per chain)")
             sel = sel.contiguous()
-        if mix is not None:
-            # defensive mixture: the same call through ais_run_mix (16-chain tiles, fp32; composes with the SMC mode)
-            mix._refuse_fast()
-            out = ops.ais_run_mix(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), tau,
-                                  noise_r, bool(trace), *mix.mix_args(), sel, True, RESAMPLE_METHODS[self.resample_method])
-            if tau is None:
-                out = out[:10]
-        elif k_moves > 0:
-            # flow-proposal moves: the same call through ais_run_moves (plain and SMC mode; the acceptance fractions come last)
-            out = ops.ais_run_moves(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), tau, noise_r,
-                                    bool(trace), RESAMPLE_METHODS[self.resample_method], k_moves, noise_g, noise_h)
-            self.last_flow_moves = out[14]
-            out = out[:14] if tau is not None else out[:10]
+        shared = (*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow))
+        if mix is None and tau is None and k_moves == 0:
+            out = ops.ais_run(*shared)
         else:
-            # SMC mode: the same call through ais_run_smc (resampling step in front of every transition, decided on the device)
-            call = ops.ais_run if tau is None else ops.ais_run_smc
-            smc = () if tau is None else (tau, noise_r, bool(trace), RESAMPLE_METHODS[self.resample_method])
-            out = call(*head, eps0, noise_a, noise_b, *slots, bool(want_base), _ops.precision_of(flow), *smc)
-        if tau is not None:
-            self.last_smc = tuple(out[10:14])
-            out = out[:10]
-        x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw = out
+            # the same call with its modes named (ais_run_ext): SMC mode (resampling step in front of every transition, decided on
+            # the device), the defensive mixture (16-chain tiles, fp32; composes with the SMC mode), flow-proposal moves
+            if mix is not None:
+                mix._refuse_fast()
+            out = ops.ais_run_ext(*shared, tau, noise_r, bool(trace), RESAMPLE_METHODS[self.resample_method],
+                                  *(mix.mix_args() if mix is not None else (None, None, None)), sel, mix is not None,
+                                  k_moves, noise_g, noise_h)
+            if tau is not None:
+                self.last_smc = tuple(out[10:14])
+            if k_moves > 0:
+                self.last_flow_moves = out[14]
+        x, lq, lp, gq, gp, log_w, n_valid, stats, base_x, base_lw = out[:10]
         point = Point(x, lq, lp, gq if hmc else None, gp if hmc else None)
         return point, log_w, n_valid, stats, base_x, base_lw
 
@@ -462,7 +456,7 @@ class AnnealedImportanceSampler:
         return float(self.alpha) if self.alpha is not None else 0.0
 
     def _call_head(self, flow, target, transition, betas=None) -> tuple:
-        """The leading arguments of ais_run / ais_run_smc / ais_phase / ais_sharded_tuned: flow image, target, betas, alpha,
+        """The leading arguments of ais_run / ais_run_ext / ais_phase / ais_sharded_tuned: flow image, target, betas, alpha,
         p_target, transition kind.  (`betas`: a per-call list in place of B_space - the stepped adaptive driver's.)"""
         op = self.transition_operator
         if bool(op.p_target) != bool(self.p_target) or (not self.p_target and op.alpha != self.alpha):

@@ -45,11 +45,11 @@ struct AisWs {
     void* ess_ws;
     size_t ess_bytes;
     int* ticket;                       // the word of the in-kernel step-size rule
-    // SMC scratch, behind the plain call's layout (which it leaves as it is); null without `smc`
+    // SMC scratch, behind the plain call's layout (which it leaves as it is); null unless the mode is on
     unsigned long long* smc_cdf;       // [B]
     int *smc_anc, *smc_flag;           // [B], [1]
     float* smc_lw;                     // [1]
-    // flow-proposal moves, behind all of it; null without `moves`
+    // flow-proposal moves, behind all of it; null unless the mode is on
     unsigned long long* mv_word;       // the accept kernel's count word
     float* mv_prop;                    // [B][3D+2] the proposal's Point
     size_t bytes;
@@ -58,7 +58,24 @@ struct AisWs {
 static PointDev prop_point(float* pb, long B, int D, bool with_grad) {
     return PointDev{pb, pb + 3 * B * D, pb + 3 * B * D + B, with_grad ? pb + B * D : nullptr, with_grad ? pb + 2 * B * D : nullptr};
 }
-static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, bool smc, bool moves = false) {
+// The optional modes of one fused call (include/fabhip.h: fabhip_ais_ext) and which of them are on.  The size function and the
+// call both resolve their `ext` here, so that size and carve cannot disagree.
+struct AisModes {
+    const fabhip_smc_args* smc;
+    const fabhip_defensive_args* mix;
+    const fabhip_flow_moves_args* moves;
+    bool smc_on, mv_on;
+    MixDev mx;                         // mx.on: the defensive mixture
+};
+static AisModes resolve_ext(const fabhip_ais_ext* ext) {
+    AisModes m{};
+    if (ext) { m.smc = ext->smc; m.mix = ext->mix; m.moves = ext->moves; }
+    m.smc_on = m.smc && m.smc->enabled != 0;
+    m.mv_on = m.moves && m.moves->n_moves > 0;
+    m.mx = make_mix_dev(m.mix);
+    return m;
+}
+static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, const AisModes& m) {
     AisWs w{};
     size_t tws = fabhip_hmc_workspace_bytes(B, D, n_inner);
     const size_t mws = fabhip_metropolis_workspace_bytes(B, D, n_inner);
@@ -73,14 +90,14 @@ static AisWs carve_ais_ws(void* workspace, long B, int D, int n_inner, bool smc,
     w.ess_ws = b.take<char>(w.ess_bytes);
     w.ticket = b.take<int>(1);
     b.take<char>(256);                 // slack
-    if (smc) {
+    if (m.smc_on) {
         w.smc_cdf = b.take<unsigned long long>((size_t)B);
         w.smc_anc = b.take<int>((size_t)B);
         char* p = b.take<char>(256);
         w.smc_flag = (int*)p;
         w.smc_lw = (float*)(p + 64);
     }
-    if (moves) {
+    if (m.mv_on) {
         w.mv_word = b.take<unsigned long long>(1);
         w.mv_prop = b.take<float>((size_t)B * (3 * D + 2));
     }
@@ -135,6 +152,31 @@ static SplineHmcWs carve_spline_hmc_ws(void* workspace, int D, int n_layers, int
     w.row_acc = b.take<float>(spline_fold_scratch_floats(B));
     w.row_dist = w.row_acc + 16 * nblk;
     w.ticket = (int*)(w.row_acc + 32 * nblk);
+    w.bytes = (size_t)(b.p - (char*)workspace) + 256;
+    return w;
+}
+
+struct SplineAisWs {
+    void* trans_ws;                    // the transition's workspace (carve_spline_hmc_ws)
+    size_t trans_bytes;
+    float* tmp;                        // [B][3D+4] compaction staging
+    int* dest;                         // [B] dest ranks
+    float *lwb, *lq0;                  // [B] log_p - log_q, [B] log q of the sampling pass
+    void* ess_ws;
+    size_t ess_bytes;
+    size_t bytes;
+};
+static SplineAisWs carve_spline_ais_ws(void* workspace, int D, int n_layers, int hidden, long B) {
+    SplineAisWs w;
+    Bump b{(char*)workspace, 256};
+    w.trans_bytes = al256(fabhip_spline_hmc_workspace_bytes(D, n_layers, hidden, B));
+    w.trans_ws = b.take<char>(w.trans_bytes);
+    w.tmp = b.take<float>((size_t)B * (3 * D + 4));
+    w.dest = b.take<int>((size_t)B);
+    w.lwb = b.take<float>((size_t)B);
+    w.lq0 = b.take<float>((size_t)B);
+    w.ess_bytes = fabhip_ess_workspace_bytes(B);
+    w.ess_ws = b.take<char>(w.ess_bytes);
     w.bytes = (size_t)(b.p - (char*)workspace) + 256;
     return w;
 }
@@ -204,6 +246,192 @@ int check_point(const fabhip_point& p, bool need_grad) {
     return FABHIP_OK;
 }
 
+// the tail of a chain phase: compaction (+ log_p - log_q) + ESS / log Z - one launch for small batches, else the separate kernels
+static int phase_tail(const fabhip_point& point, float* log_w, long B, int dim, const int* n_in, int* n_out, float* tmp, int* dest,
+                      float* extra, float* diff, double n_norm, float* stats_out, void* ess_ws, size_t ess_bytes, float* base_x,
+                      int* zero_word, float* zero_f, hipStream_t st) {
+    int rc = FABHIP_ENOTSUP;
+    if (option(FABHIP_OPT_FUSED_TAIL) != 0) {
+        TailArgs t;
+        t.x = point.x; t.lq = point.log_q; t.lp = point.log_p; t.gq = point.grad_log_q; t.gp = point.grad_log_p;
+        t.log_w = log_w; t.extra = extra; t.n_in = n_in; t.n_out = n_out; t.B = B; t.D = dim; t.diff = diff; t.n_norm = n_norm;
+        t.stats_out = stats_out; t.zero_word = zero_word; t.zero_f = zero_f; t.n_zero_f = zero_f ? 10 : 0;
+        rc = tail_small(t, dest, st);
+        if (rc != FABHIP_OK && rc != FABHIP_ENOTSUP) return rc;
+    }
+    if (rc == FABHIP_ENOTSUP) {
+        if (zero_word && hipMemsetAsync(zero_word, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
+        if (zero_f && hipMemsetAsync(zero_f, 0, 10 * 4, st) != hipSuccess) return FABHIP_ELAUNCH;
+        FAB_TRY(compact_rows(point, log_w, B, dim, n_in, n_out, tmp, dest, extra, st));
+    }
+    if (base_x &&         // the compacted starting points (rows beyond the count are don't-care)
+        hipMemcpyAsync(base_x, point.x, (size_t)B * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return FABHIP_ELAUNCH;
+    if (rc == FABHIP_ENOTSUP) {
+        if (diff) launch_sub(point.log_p, point.log_q, diff, B, st);
+        FAB_TRY(fabhip_ess_logz(diff ? diff : log_w, B, n_out, n_norm, stats_out, ess_ws, ess_bytes, (fabhip_stream_t)st));
+    }
+    return check_launch();
+}
+
+// ---- the fused AIS call (RealNVP family), step by step; fabhip_ais_phase_ext strings the steps together ---------------------------
+// The argument checks of a call that runs `phases` and the transitions j_begin .. j_end, in the precedence of their return codes
+// (the workspace size comes behind them: the caller carves with `*modes`).
+static int check_ais_call(const fabhip_ais_args* a, const fabhip_ais_ext* ext, int32_t phases, int32_t j_begin, int32_t j_end,
+                          const float* partials, AisModes* modes) {
+    if (!a || !a->flow.packed || !a->betas || !a->step_state || !a->log_w ||
+        !a->n_valid || !a->stats || !a->workspace || a->B < 1 || a->M < 1 || a->n_inner < 1)
+        return FABHIP_EINVAL;
+    if (j_begin <= j_end && (!a->noise_a || !a->noise_b)) return FABHIP_EINVAL;       // (read by the transitions only)
+    const bool do_init = (phases & FABHIP_AIS_INIT) != 0;
+    if (do_init && !a->eps0) return FABHIP_EINVAL;
+    if (j_begin <= j_end && (j_begin < 1 || j_end > a->M)) return FABHIP_EINVAL;
+    if (partials && a->transition == FABHIP_TRANSITION_HMC && j_begin != j_end) return FABHIP_ENOTSUP;
+    const bool hmc = a->transition == FABHIP_TRANSITION_HMC;
+    if (!hmc && a->transition != FABHIP_TRANSITION_METROPOLIS) return FABHIP_EINVAL;
+    if (hmc && (!a->common_epsilon || !a->mass)) return FABHIP_EINVAL;
+    FAB_TRY(check_flow_shape(a->flow.dim, a->flow.n_layers, a->flow.width));
+    FAB_TRY(check_target(&a->target, a->flow.dim));
+    FAB_TRY(check_point(a->point, hmc));
+    const AisModes m = resolve_ext(ext);
+    FAB_TRY(check_mix(m.mix));
+    if (m.mx.on && (partials || resolve_fast(a->flow.precision))) return FABHIP_ENOTSUP;  // (sharded chains, bf16 fast mode)
+    if (m.mx.on && do_init && !m.mix->sel) return FABHIP_EINVAL;                          // (like eps0: read by INIT only)
+    if (m.smc_on && partials) return FABHIP_ENOTSUP;
+    if (m.smc_on && m.smc->method != FABHIP_SMC_SYSTEMATIC && m.smc->method != FABHIP_SMC_STRATIFIED) return FABHIP_EINVAL;
+    if (m.smc_on && j_begin <= j_end && !m.smc->u) return FABHIP_EINVAL;              // (like the noise: read by the transitions only)
+    if (m.moves && m.moves->n_moves < 0) return FABHIP_EINVAL;
+    if (m.mv_on && (partials || m.mx.on)) return FABHIP_ENOTSUP;                      // (sharded chains, defensive mixture)
+    if (m.mv_on && j_begin <= j_end && (!m.moves->noise_g || !m.moves->noise_h)) return FABHIP_EINVAL;
+    if (m.mv_on && a->B > 0x3fffffffL) return FABHIP_EINVAL;
+    *modes = m;
+    return FABHIP_OK;
+}
+
+// what the steps of one call share
+struct AisCall {
+    const fabhip_ais_args* a;
+    AisModes m;
+    AisWs w;
+    FlowDims f;
+    TargetDev tg;
+    bool hmc;
+    int* ticket;                       // the word of the in-kernel step-size rule (hmc_adapt_last), or null: k_hmc_adapt launches
+    float* partials;
+    hipStream_t st;
+};
+
+// 1. chain initialisation, 2. remove nan/inf ("chain init"), 3. ESS over the base samples (ais.py:68-71) -> stats[0..2]
+static int ais_chain_init(const AisCall& c) {
+    const fabhip_ais_args* a = c.a;
+    const AisWs& w = c.w;
+    const FlowDims& f = c.f;
+    const long B = a->B;
+    const int hmc = c.hmc ? 1 : 0;
+    fabhip_anneal a1;
+    fabhip_anneal_coefs(a->betas[1], a->alpha, a->p_target, &a1);
+    const PointDev pt = make_point_dev(a->point);
+    if (c.m.mx.on) {
+        FAB_TRY(ais_init_t16(f, a->flow.packed, c.tg, a->eps0, pt, a->log_w, a->base_log_w, a1, hmc, B, c.m.mx, c.m.mix->sel, c.st));
+    } else if (hmc && use_r8_tiles(f, B)) {
+        FAB_TRY(fabhip_flow_sample(&a->flow, a->eps0, a->point.x, w.lwb, B, (fabhip_stream_t)c.st));
+        FAB_TRY(ais_init_r8(f, a->flow.packed, c.tg, w.lwb, pt, a->log_w, a->base_log_w, a1, B, c.st));
+    } else if (hmc && use_r4_tiles(f, B) && option(FABHIP_OPT_R4_STREAM) != 0) {
+        // 4-chain tiles: x, log q0 = flow.sample(eps0), then log q + d/dx (the reference re-evaluates: base.py:65-68), target,
+        // log w - one kernel where the stream image exists (f.o_r4s), else the flow-sample kernel first
+        if (f.o_r4s >= 0 && f.NTW / 4 >= 2) {
+            FAB_TRY(ais_init_r4(f, a->flow.packed, c.tg, nullptr, a->eps0, pt, a->log_w, a->base_log_w, a1, B, c.st));
+        } else {
+            FAB_TRY(fabhip_flow_sample(&a->flow, a->eps0, a->point.x, w.lwb, B, (fabhip_stream_t)c.st));
+            FAB_TRY(ais_init_r4(f, a->flow.packed, c.tg, w.lwb, nullptr, pt, a->log_w, a->base_log_w, a1, B, c.st));
+        }
+    } else {
+        FAB_TRY(ais_init_t16(f, a->flow.packed, c.tg, a->eps0, pt, a->log_w, a->base_log_w, a1, hmc, B, MixDev{}, nullptr, c.st));
+    }
+    return phase_tail(a->point, a->log_w, B, f.D, nullptr, a->n_valid, w.tmp, w.dest, a->base_log_w, w.lwb, 1.0, a->stats + 0,
+                      w.ess_ws, w.ess_bytes, a->base_x, c.ticket, a->stats + 6, c.st);
+}
+
+// resampling step of transition j (log_w targets the distribution this transition leaves invariant): decision,
+// gather into the staging buffer, copy back - three launches whatever the decision.  No transition kernel keeps
+// per-chain state in the workspace from one transition to the next (part_* / row_* / the proposal buffer are
+// written and consumed inside one transition), so the point and log_w are all there is to move.
+static int ais_resample_step(const AisCall& c, int j) {
+    const fabhip_ais_args* a = c.a;
+    const fabhip_smc_args* smc = c.m.smc;
+    const AisWs& w = c.w;
+    const long B = a->B;
+    SmcK k;
+    k.log_w = a->log_w; k.n_ptr = a->n_valid; k.B = B; k.tau = smc->tau; k.u = smc->u + (j - 1);
+    k.cdf = w.smc_cdf; k.anc = w.smc_anc; k.flag = w.smc_flag; k.lw_common = w.smc_lw;
+    k.resampled_out = smc->resampled ? smc->resampled + (j - 1) : nullptr;
+    k.ess_out = smc->ess ? smc->ess + (j - 1) : nullptr;
+    k.anc_out = smc->ancestors ? smc->ancestors + (size_t)(j - 1) * B : nullptr;
+    k.lw_pre_out = smc->log_w_pre ? smc->log_w_pre + (size_t)(j - 1) * B : nullptr;
+    k.method = smc->method;
+    FAB_TRY(smc_decide(k, c.st));
+    return smc_gather_copyback(a->point, a->log_w, w.tmp, w.smc_anc, w.smc_flag, w.smc_lw, a->n_valid, B, c.f.D, c.st);
+}
+
+// global moves of step j at beta_j (coefficients `cj`), behind the resampling step and in front of the local transition: three
+// launches each; they neither read nor write log_w, the step sizes or the ticket word
+static int ais_moves_step(const AisCall& c, int j, fabhip_anneal cj) {
+    const fabhip_ais_args* a = c.a;
+    const fabhip_flow_moves_args* moves = c.m.moves;
+    const long B = a->B;
+    const int D = c.f.D, k = moves->n_moves;
+    for (int m = 0; m < k; ++m) {
+        const size_t slab = (size_t)(j - 1) * k + m;
+        FAB_TRY(flow_move_impl(a->flow, a->target, a->point, B, a->n_valid, cj, moves->noise_g + slab * B * D,
+                               moves->noise_h + slab * B, moves->p_accept_out ? moves->p_accept_out + slab : nullptr,
+                               nullptr, c.w.mv_word, c.w.mv_prop, c.st));
+    }
+    return FABHIP_OK;
+}
+
+// transition j, HMC or Metropolis, from beta_j (`cj`) towards beta_{j+1} (`cn`)
+static int ais_transition(const AisCall& c, int j, fabhip_anneal cj, fabhip_anneal cn) {
+    const fabhip_ais_args* a = c.a;
+    const AisWs& w = c.w;
+    const long B = a->B;
+    const int D = c.f.D;
+    float* lw = (a->betas[j + 1] != a->betas[j]) ? a->log_w : nullptr;      // ais.py:93
+    const size_t nslab = (size_t)(j - 1) * a->n_inner;
+    if (c.hmc) {
+        fabhip_hmc_args h;
+        h.flow = a->flow; h.target = a->target; h.point = a->point; h.B = B; h.n_valid = a->n_valid;
+        h.cur = cj; h.next = cn; h.log_w = lw;
+        h.noise_p = a->noise_a + nslab * B * D; h.noise_e = a->noise_b + nslab * B;
+        h.epsilons = a->step_state + nslab; h.common_epsilon = a->common_epsilon; h.mass = a->mass;
+        h.n_outer = a->n_inner; h.L = a->L; h.max_grad = a->max_grad; h.target_p_accept = a->target_p_accept;
+        h.tune = a->tune;
+        h.p_accept = nullptr; h.avg_distance = nullptr;
+        h.workspace = w.trans_ws; h.workspace_bytes = w.trans_bytes;
+        h.partials = c.partials;
+        // logging slots of the first / last distribution (hmc.py:173-183), one acceptance per outer loop
+        if (j == 1) { h.p_accept = a->p_accept_first; h.avg_distance = a->avg_distance_first; }
+        else if (j == a->M) { h.p_accept = a->p_accept_last; h.avg_distance = a->avg_distance_last; }
+        return hmc_transition_impl(&h, c.st, c.ticket, c.m.mx);
+    }
+    fabhip_metropolis_args m;
+    m.flow = a->flow; m.target = a->target; m.point = a->point; m.B = B; m.n_valid = a->n_valid;
+    m.cur = cj; m.next = cn; m.log_w = lw;
+    m.noise_x = a->noise_a + nslab * B * D; m.noise_u = a->noise_b + nslab * B;
+    m.noise_scalings = a->step_state + nslab; m.n_updates = a->n_inner;
+    m.target_p_accept = a->target_p_accept; m.tune = a->tune;
+    m.workspace = w.trans_ws; m.workspace_bytes = w.trans_bytes;
+    // deferred rule: transition j's block sums + count at slab offset (j - 1) (n_updates nblk + 1)
+    return metropolis_transition_impl(&m, c.st, c.partials ? c.partials + (size_t)(j - 1) * ((size_t)a->n_inner * nblk_of(B) + 1)
+                                                           : nullptr, c.m.mx);
+}
+
+// 5. remove nan/inf ("chain end"), 6. ESS / log Z over the survivors (ais.py:77-86) -> stats[3..5]
+static int ais_finish(const AisCall& c) {
+    const fabhip_ais_args* a = c.a;
+    return phase_tail(a->point, a->log_w, a->B, c.f.D, a->n_valid, a->n_valid + 1, c.w.tmp, c.w.dest, nullptr, nullptr, (double)a->B,
+                      a->stats + 3, c.w.ess_ws, c.w.ess_bytes, nullptr, nullptr, nullptr, c.st);
+}
+
 }  // namespace fab
 
 using namespace fab;
@@ -255,38 +483,10 @@ int fabhip_metropolis_transition(const fabhip_metropolis_args* a, fabhip_stream_
 }
 
 // ---- whole AIS call -------------------------------------------------------------------------------
-size_t fabhip_ais_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner) { return carve_ais_ws(nullptr, B, dim, n_inner, false).bytes; }
+size_t fabhip_ais_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner) { return fabhip_ais_ext_workspace_bytes(B, dim, n_inner, nullptr); }
 
-size_t fabhip_ais_smc_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner) {
-    return carve_ais_ws(nullptr, B, dim, n_inner, true).bytes;
-}
-
-// the tail of a chain phase: compaction (+ log_p - log_q) + ESS / log Z - one launch for small batches, else the separate kernels
-static int phase_tail(const fabhip_point& point, float* log_w, long B, int dim, const int* n_in, int* n_out, float* tmp, int* dest,
-                      float* extra, float* diff, double n_norm, float* stats_out, void* ess_ws, size_t ess_bytes, float* base_x,
-                      int* zero_word, float* zero_f, hipStream_t st) {
-    int rc = FABHIP_ENOTSUP;
-    if (option(FABHIP_OPT_FUSED_TAIL) != 0) {
-        TailArgs t;
-        t.x = point.x; t.lq = point.log_q; t.lp = point.log_p; t.gq = point.grad_log_q; t.gp = point.grad_log_p;
-        t.log_w = log_w; t.extra = extra; t.n_in = n_in; t.n_out = n_out; t.B = B; t.D = dim; t.diff = diff; t.n_norm = n_norm;
-        t.stats_out = stats_out; t.zero_word = zero_word; t.zero_f = zero_f; t.n_zero_f = zero_f ? 10 : 0;
-        rc = tail_small(t, dest, st);
-        if (rc != FABHIP_OK && rc != FABHIP_ENOTSUP) return rc;
-    }
-    if (rc == FABHIP_ENOTSUP) {
-        if (zero_word && hipMemsetAsync(zero_word, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
-        if (zero_f && hipMemsetAsync(zero_f, 0, 10 * 4, st) != hipSuccess) return FABHIP_ELAUNCH;
-        FAB_TRY(compact_rows(point, log_w, B, dim, n_in, n_out, tmp, dest, extra, st));
-    }
-    if (base_x &&         // the compacted starting points (rows beyond the count are don't-care)
-        hipMemcpyAsync(base_x, point.x, (size_t)B * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return FABHIP_ELAUNCH;
-    if (rc == FABHIP_ENOTSUP) {
-        if (diff) launch_sub(point.log_p, point.log_q, diff, B, st);
-        FAB_TRY(fabhip_ess_logz(diff ? diff : log_w, B, n_out, n_norm, stats_out, ess_ws, ess_bytes, (fabhip_stream_t)st));
-    }
-    return check_launch();
+size_t fabhip_ais_ext_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, const fabhip_ais_ext* ext) {
+    return carve_ais_ws(nullptr, B, dim, n_inner, resolve_ext(ext)).bytes;
 }
 
 // ---- spline flow as base distribution (csrc/spline_stream.hip, spline_tile16.hip) ------------------------------------------------------
@@ -370,11 +570,7 @@ int fabhip_spline_hmc_transition(const fabhip_spline_hmc_args* a, fabhip_stream_
 }
 
 size_t fabhip_spline_ais_workspace_bytes(int32_t dim, int32_t n_layers, int32_t hidden, int64_t B) {
-    size_t s = al256(fabhip_spline_hmc_workspace_bytes(dim, n_layers, hidden, B));
-    s += al256((size_t)B * (3 * dim + 4) * 4);    // compaction staging
-    s += 3 * al256((size_t)B * 4);                // dest ranks, log_p - log_q, log q of the sampling pass
-    s += al256(fabhip_ess_workspace_bytes(B));
-    return s + 256;
+    return carve_spline_ais_ws(nullptr, dim, n_layers, hidden, B).bytes;
 }
 
 int fabhip_spline_ais_run(const fabhip_spline_ais_args* a, fabhip_stream_t stream) {
@@ -386,29 +582,21 @@ int fabhip_spline_ais_run(const fabhip_spline_ais_args* a, fabhip_stream_t strea
     FAB_TRY(check_point(a->point, true));
     const int D = a->flow.dim;
     const long B = a->B;
-    if (a->workspace_bytes < fabhip_spline_ais_workspace_bytes(D, a->flow.n_layers, a->flow.hidden, B)) return FABHIP_ENOSPC;
+    const SplineAisWs w = carve_spline_ais_ws(a->workspace, D, a->flow.n_layers, a->flow.hidden, B);
+    if (a->workspace_bytes < w.bytes) return FABHIP_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)a->workspace;
-    const size_t tws = al256(fabhip_spline_hmc_workspace_bytes(D, a->flow.n_layers, a->flow.hidden, B));
-    void* trans_ws = ws; ws += tws;
-    float* tmp = (float*)ws; ws += al256((size_t)B * (3 * D + 4) * 4);
-    int* dest = (int*)ws; ws += al256((size_t)B * 4);
-    float* lwb = (float*)ws; ws += al256((size_t)B * 4);
-    float* lq0 = (float*)ws; ws += al256((size_t)B * 4);
-    void* ess_ws = ws;
-    const size_t ess_bytes = fabhip_ess_workspace_bytes(B);
     // the spline kernels' own scratch: the transition workspace is free until the first transition
     const size_t sb = fabhip_spline_workspace_bytes(D, a->flow.n_layers, a->flow.hidden, B, 1);
     // 1. chain initialisation: x, log q0 = flow.sample ; point = create_point(x) ; log_w = pi_beta1(point) - log q0
-    FAB_TRY(fabhip_spline_sample(&a->flow, a->u0, a->eps0, a->point.x, lq0, B, trans_ws, sb, stream));
-    FAB_TRY(fabhip_spline_log_prob(&a->flow, a->point.x, a->point.log_q, a->point.grad_log_q, B, trans_ws, sb, stream));
+    FAB_TRY(fabhip_spline_sample(&a->flow, a->u0, a->eps0, a->point.x, w.lq0, B, w.trans_ws, sb, stream));
+    FAB_TRY(fabhip_spline_log_prob(&a->flow, a->point.x, a->point.log_q, a->point.grad_log_q, B, w.trans_ws, sb, stream));
     FAB_TRY(fabhip_target_log_prob(&a->target, a->point.x, a->point.log_p, a->point.grad_log_p, B, stream));
     fabhip_anneal a1;
     fabhip_anneal_coefs(a->betas[1], a->alpha, a->p_target, &a1);
-    launch_spline_init_logw(a->point.log_q, a->point.log_p, lq0, a1, a->log_w, a->base_log_w, B, st);
+    launch_spline_init_logw(a->point.log_q, a->point.log_p, w.lq0, a1, a->log_w, a->base_log_w, B, st);
     // 2. "chain init" filter, 3. base ESS
-    FAB_TRY(phase_tail(a->point, a->log_w, B, D, nullptr, a->n_valid, tmp, dest, a->base_log_w, lwb, 1.0, a->stats + 0, ess_ws,
-                       ess_bytes, a->base_x, nullptr, a->stats + 6, st));
+    FAB_TRY(phase_tail(a->point, a->log_w, B, D, nullptr, a->n_valid, w.tmp, w.dest, a->base_log_w, w.lwb, 1.0, a->stats + 0, w.ess_ws,
+                       w.ess_bytes, a->base_x, nullptr, a->stats + 6, st));
     // 4. transitions
     for (int j = 1; j <= a->M; ++j) {
         fabhip_spline_hmc_args h;
@@ -423,57 +611,68 @@ int fabhip_spline_ais_run(const fabhip_spline_ais_args* a, fabhip_stream_t strea
         h.p_accept = nullptr; h.avg_distance = nullptr;
         if (j == 1) { h.p_accept = a->p_accept_first; h.avg_distance = a->avg_distance_first; }
         else if (j == a->M) { h.p_accept = a->p_accept_last; h.avg_distance = a->avg_distance_last; }
-        h.workspace = trans_ws; h.workspace_bytes = tws;
+        h.workspace = w.trans_ws; h.workspace_bytes = w.trans_bytes;
         if (j == 1 && spline_leap_fold_supported(&a->flow, B) &&
-            hipMemsetAsync(carve_spline_hmc_ws(trans_ws, D, a->flow.n_layers, a->flow.hidden, B).ticket, 0, 4, st) != hipSuccess)
+            hipMemsetAsync(carve_spline_hmc_ws(w.trans_ws, D, a->flow.n_layers, a->flow.hidden, B).ticket, 0, 4, st) != hipSuccess)
             return FABHIP_ELAUNCH;
         FAB_TRY(spline_hmc_transition_impl(&h, stream, true));
     }
     // 5. "chain end" filter, 6. ESS / log Z
-    FAB_TRY(phase_tail(a->point, a->log_w, B, D, a->n_valid, a->n_valid + 1, tmp, dest, nullptr, nullptr, (double)B, a->stats + 3,
-                       ess_ws, ess_bytes, nullptr, nullptr, nullptr, st));
+    FAB_TRY(phase_tail(a->point, a->log_w, B, D, a->n_valid, a->n_valid + 1, w.tmp, w.dest, nullptr, nullptr, (double)B, a->stats + 3,
+                       w.ess_ws, w.ess_bytes, nullptr, nullptr, nullptr, st));
     return check_launch();
 }
 
-int fabhip_ais_run(const fabhip_ais_args* a, fabhip_stream_t stream) {
-    if (!a) return FABHIP_EINVAL;
-    return fabhip_ais_phase_smc(a, nullptr, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
-}
+int fabhip_ais_run(const fabhip_ais_args* a, fabhip_stream_t stream) { return fabhip_ais_run_ext(a, nullptr, stream); }
 
 int fabhip_ais_phase(const fabhip_ais_args* a, int32_t phases, int32_t j_begin, int32_t j_end, float* partials,
                      fabhip_stream_t stream) {
-    return fabhip_ais_phase_smc(a, nullptr, phases, j_begin, j_end, partials, stream);
+    return fabhip_ais_phase_ext(a, nullptr, phases, j_begin, j_end, partials, stream);
 }
 
-int fabhip_ais_run_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, fabhip_stream_t stream) {
+int fabhip_ais_run_ext(const fabhip_ais_args* a, const fabhip_ais_ext* ext, fabhip_stream_t stream) {
     if (!a) return FABHIP_EINVAL;
-    return fabhip_ais_phase_smc(a, smc, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+    return fabhip_ais_phase_ext(a, ext, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
 }
 
-int fabhip_ais_phase_smc(const fabhip_ais_args* a, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin, int32_t j_end,
+int fabhip_ais_phase_ext(const fabhip_ais_args* a, const fabhip_ais_ext* ext, int32_t phases, int32_t j_begin, int32_t j_end,
                          float* partials, fabhip_stream_t stream) {
-    return fabhip_ais_phase_mix(a, smc, nullptr, phases, j_begin, j_end, partials, stream);
-}
-
-int fabhip_ais_run_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                       fabhip_stream_t stream) {
-    if (!a) return FABHIP_EINVAL;
-    return fabhip_ais_phase_mix(a, smc, mix, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
-}
-
-int fabhip_ais_phase_mix(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix, int32_t phases,
-                         int32_t j_begin, int32_t j_end, float* partials, fabhip_stream_t stream) {
-    return fabhip_ais_phase_moves(a, smc, mix, nullptr, phases, j_begin, j_end, partials, stream);
-}
-
-size_t fabhip_ais_moves_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, int32_t smc) {
-    return carve_ais_ws(nullptr, B, dim, n_inner, smc != 0, true).bytes;
-}
-
-int fabhip_ais_run_moves(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                         const fabhip_flow_moves_args* moves, fabhip_stream_t stream) {
-    if (!a) return FABHIP_EINVAL;
-    return fabhip_ais_phase_moves(a, smc, mix, moves, FABHIP_AIS_INIT | FABHIP_AIS_FINISH, 1, a->M, nullptr, stream);
+    AisCall c;
+    FAB_TRY(check_ais_call(a, ext, phases, j_begin, j_end, partials, &c.m));
+    const bool ws_kept = (phases & (FABHIP_AIS_INIT | FABHIP_AIS_CONTINUE)) != 0;     // the ticket word of this workspace is zero
+    c.a = a; c.partials = partials; c.st = (hipStream_t)stream; c.hmc = a->transition == FABHIP_TRANSITION_HMC;
+    c.w = carve_ais_ws(a->workspace, a->B, a->flow.dim, a->n_inner, c.m);
+    if (a->workspace_bytes < c.w.bytes) return FABHIP_ENOSPC;
+    // (the accept kernel leaves its count word zero: one 8-byte fill per call that runs moves)
+    if (c.m.mv_on && j_begin <= j_end && hipMemsetAsync(c.w.mv_word, 0, 8, c.st) != hipSuccess) return FABHIP_ELAUNCH;
+    c.f = flow_dims_of(a->flow);
+    c.tg = make_target_dev(a->target);
+    // step-size rule inside the transition kernels (hmc_adapt_last): only where the ticket word is known to be zero (this call's or,
+    // with FABHIP_AIS_CONTINUE, an earlier call's init phase zeroed it; every transition kernel leaves it zero)
+    c.ticket = (c.hmc && !c.m.mx.on && !partials && option(FABHIP_OPT_ADAPT_FOLD) != 0 && nblk_of(a->B) <= 2048 &&
+                (use_r8_tiles(c.f, a->B) || use_r4_tiles(c.f, a->B))) ? c.w.ticket : nullptr;     // (2 nblk floats of LDS scratch)
+    // (round 6: a call that runs transitions on a workspace nobody zeroed - the second piece of a call whose INIT piece was its own
+    //  fabhip_ais_phase call, fab_torch_amd/ais.py: repeated calls - zeroes the word itself: one 4-byte fill instead of a
+    //  k_hmc_adapt launch per transition)
+    if (c.ticket && !ws_kept) {
+        if (j_begin > j_end) c.ticket = nullptr;
+        else if (hipMemsetAsync(c.ticket, 0, 4, c.st) != hipSuccess) return FABHIP_ELAUNCH;
+    }
+    if (phases & FABHIP_AIS_INIT) FAB_TRY(ais_chain_init(c));
+    // 4. transitions: [resampling step,] [moves,] transition j
+    for (int j = j_begin; j <= j_end; ++j) {
+        fabhip_anneal cj, cn;
+        fabhip_anneal_coefs(a->betas[j], a->alpha, a->p_target, &cj);
+        fabhip_anneal_coefs(a->betas[j + 1], a->alpha, a->p_target, &cn);
+        if (c.m.smc_on) {
+            FAB_TRY(ais_resample_step(c, j));
+            if (c.m.smc->only_resample) continue;
+        }
+        if (c.m.mv_on) FAB_TRY(ais_moves_step(c, j, cj));
+        FAB_TRY(ais_transition(c, j, cj, cn));
+    }
+    if (phases & FABHIP_AIS_FINISH) FAB_TRY(ais_finish(c));
+    return check_launch();
 }
 
 size_t fabhip_flow_move_workspace_bytes(int64_t B, int32_t dim) {
@@ -499,156 +698,6 @@ int fabhip_flow_move(const fabhip_flow_move_args* a, fabhip_stream_t stream) {
     }
     return flow_move_impl(a->flow, a->target, a->point, (long)a->B, a->n_valid, a->cur, a->noise_g, a->noise_h, a->p_accept,
                           a->n_accept, w.word, w.prop, st);
-}
-
-int fabhip_ais_phase_moves(const fabhip_ais_args* a, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                           const fabhip_flow_moves_args* moves, int32_t phases, int32_t j_begin, int32_t j_end, float* partials,
-                           fabhip_stream_t stream) {
-    if (!a || !a->flow.packed || !a->betas || !a->step_state || !a->log_w ||
-        !a->n_valid || !a->stats || !a->workspace || a->B < 1 || a->M < 1 || a->n_inner < 1)
-        return FABHIP_EINVAL;
-    if (j_begin <= j_end && (!a->noise_a || !a->noise_b)) return FABHIP_EINVAL;       // (read by the transitions only)
-    const bool do_init = (phases & FABHIP_AIS_INIT) != 0, do_finish = (phases & FABHIP_AIS_FINISH) != 0;
-    const bool ws_kept = do_init || (phases & FABHIP_AIS_CONTINUE) != 0;              // the ticket word of this workspace is zero
-    if (do_init && !a->eps0) return FABHIP_EINVAL;
-    if (j_begin <= j_end && (j_begin < 1 || j_end > a->M)) return FABHIP_EINVAL;
-    if (partials && a->transition == FABHIP_TRANSITION_HMC && j_begin != j_end) return FABHIP_ENOTSUP;
-    const bool hmc = a->transition == FABHIP_TRANSITION_HMC;
-    if (!hmc && a->transition != FABHIP_TRANSITION_METROPOLIS) return FABHIP_EINVAL;
-    if (hmc && (!a->common_epsilon || !a->mass)) return FABHIP_EINVAL;
-    FAB_TRY(check_flow_shape(a->flow.dim, a->flow.n_layers, a->flow.width));
-    FAB_TRY(check_target(&a->target, a->flow.dim));
-    FAB_TRY(check_point(a->point, hmc));
-    const bool smc_on = smc && smc->enabled != 0;
-    FAB_TRY(check_mix(mix));
-    const MixDev mx = make_mix_dev(mix);
-    if (mx.on && (partials || resolve_fast(a->flow.precision))) return FABHIP_ENOTSUP;    // (sharded chains, bf16 fast mode)
-    if (mx.on && do_init && !mix->sel) return FABHIP_EINVAL;                              // (like eps0: read by INIT only)
-    if (smc_on && partials) return FABHIP_ENOTSUP;
-    if (smc_on && smc->method != FABHIP_SMC_SYSTEMATIC && smc->method != FABHIP_SMC_STRATIFIED) return FABHIP_EINVAL;
-    if (smc_on && j_begin <= j_end && !smc->u) return FABHIP_EINVAL;                  // (like the noise: read by the transitions only)
-    if (moves && moves->n_moves < 0) return FABHIP_EINVAL;
-    const bool mv_on = moves && moves->n_moves > 0;
-    if (mv_on && (partials || mx.on)) return FABHIP_ENOTSUP;                          // (sharded chains, defensive mixture)
-    if (mv_on && j_begin <= j_end && (!moves->noise_g || !moves->noise_h)) return FABHIP_EINVAL;
-    if (mv_on && a->B > 0x3fffffffL) return FABHIP_EINVAL;
-    const AisWs w = carve_ais_ws(a->workspace, a->B, a->flow.dim, a->n_inner, smc_on, mv_on);
-    if (a->workspace_bytes < w.bytes) return FABHIP_ENOSPC;
-    hipStream_t st = (hipStream_t)stream;
-    // (the accept kernel leaves its count word zero: one 8-byte fill per call that runs moves)
-    if (mv_on && j_begin <= j_end && hipMemsetAsync(w.mv_word, 0, 8, st) != hipSuccess) return FABHIP_ELAUNCH;
-    const FlowDims f = flow_dims_of(a->flow);
-    const TargetDev tg = make_target_dev(a->target);
-    const int D = f.D;
-    const long B = a->B;
-    // step-size rule inside the transition kernels (hmc_adapt_last): only where the ticket word is known to be zero (this call's or,
-    // with FABHIP_AIS_CONTINUE, an earlier call's init phase zeroed it; every transition kernel leaves it zero)
-    int* ticket = (hmc && !mx.on && !partials && option(FABHIP_OPT_ADAPT_FOLD) != 0 && nblk_of(B) <= 2048 &&
-                   (use_r8_tiles(f, B) || use_r4_tiles(f, B))) ? w.ticket : nullptr;      // (2 nblk floats of LDS scratch)
-    // (round 6: a call that runs transitions on a workspace nobody zeroed - the second piece of a call whose INIT piece was its own
-    //  fabhip_ais_phase call, fab_torch_amd/ais.py: repeated calls - zeroes the word itself: one 4-byte fill instead of a
-    //  k_hmc_adapt launch per transition)
-    if (ticket && !ws_kept) {
-        if (j_begin > j_end) ticket = nullptr;
-        else if (hipMemsetAsync(ticket, 0, 4, st) != hipSuccess) return FABHIP_ELAUNCH;
-    }
-
-    if (do_init) {
-    // 1. chain initialisation
-    fabhip_anneal a1;
-    fabhip_anneal_coefs(a->betas[1], a->alpha, a->p_target, &a1);
-    {
-        const PointDev pt = make_point_dev(a->point);
-        if (mx.on) {
-            FAB_TRY(ais_init_t16(f, a->flow.packed, tg, a->eps0, pt, a->log_w, a->base_log_w, a1, hmc ? 1 : 0, B, mx, mix->sel, st));
-        } else if (hmc && use_r8_tiles(f, B)) {
-            FAB_TRY(fabhip_flow_sample(&a->flow, a->eps0, a->point.x, w.lwb, B, stream));
-            FAB_TRY(ais_init_r8(f, a->flow.packed, tg, w.lwb, pt, a->log_w, a->base_log_w, a1, B, st));
-        } else if (hmc && use_r4_tiles(f, B) && option(FABHIP_OPT_R4_STREAM) != 0) {
-            // 4-chain tiles: x, log q0 = flow.sample(eps0), then log q + d/dx (the reference re-evaluates: base.py:65-68), target,
-            // log w - one kernel where the stream image exists (f.o_r4s), else the flow-sample kernel first
-            if (f.o_r4s >= 0 && f.NTW / 4 >= 2) {
-                FAB_TRY(ais_init_r4(f, a->flow.packed, tg, nullptr, a->eps0, pt, a->log_w, a->base_log_w, a1, B, st));
-            } else {
-                FAB_TRY(fabhip_flow_sample(&a->flow, a->eps0, a->point.x, w.lwb, B, stream));
-                FAB_TRY(ais_init_r4(f, a->flow.packed, tg, w.lwb, nullptr, pt, a->log_w, a->base_log_w, a1, B, st));
-            }
-        } else {
-            FAB_TRY(ais_init_t16(f, a->flow.packed, tg, a->eps0, pt, a->log_w, a->base_log_w, a1, hmc ? 1 : 0, B, MixDev{}, nullptr, st));
-        }
-    }
-    // 2. remove nan/inf ("chain init"), 3. ESS over the base samples (ais.py:68-71) -> stats[0..2]
-    FAB_TRY(phase_tail(a->point, a->log_w, B, D, nullptr, a->n_valid, w.tmp, w.dest, a->base_log_w, w.lwb, 1.0, a->stats + 0,
-                       w.ess_ws, w.ess_bytes, a->base_x, ticket, a->stats + 6, st));
-    }
-    // 4. transitions
-    for (int j = j_begin; j <= j_end; ++j) {
-        fabhip_anneal cj, cn;
-        fabhip_anneal_coefs(a->betas[j], a->alpha, a->p_target, &cj);
-        fabhip_anneal_coefs(a->betas[j + 1], a->alpha, a->p_target, &cn);
-        float* lw = (a->betas[j + 1] != a->betas[j]) ? a->log_w : nullptr;      // ais.py:93
-        const size_t nslab = (size_t)(j - 1) * a->n_inner;
-        if (smc_on) {
-            // resampling step of transition j (log_w targets the distribution this transition leaves invariant): decision,
-            // gather into the staging buffer, copy back - three launches whatever the decision.  No transition kernel keeps
-            // per-chain state in the workspace from one transition to the next (part_* / row_* / the proposal buffer are
-            // written and consumed inside one transition), so the point and log_w are all there is to move.
-            SmcK k;
-            k.log_w = a->log_w; k.n_ptr = a->n_valid; k.B = B; k.tau = smc->tau; k.u = smc->u + (j - 1);
-            k.cdf = w.smc_cdf; k.anc = w.smc_anc; k.flag = w.smc_flag; k.lw_common = w.smc_lw;
-            k.resampled_out = smc->resampled ? smc->resampled + (j - 1) : nullptr;
-            k.ess_out = smc->ess ? smc->ess + (j - 1) : nullptr;
-            k.anc_out = smc->ancestors ? smc->ancestors + (size_t)(j - 1) * B : nullptr;
-            k.lw_pre_out = smc->log_w_pre ? smc->log_w_pre + (size_t)(j - 1) * B : nullptr;
-            k.method = smc->method;
-            FAB_TRY(smc_decide(k, st));
-            FAB_TRY(smc_gather_copyback(a->point, a->log_w, w.tmp, w.smc_anc, w.smc_flag, w.smc_lw, a->n_valid, B, D, st));
-            if (smc->only_resample) continue;
-        }
-        if (mv_on) {
-            // global moves of step j at beta_j, behind the resampling step and in front of the local transition: three launches
-            // each; they neither read nor write log_w, the step sizes or the ticket word
-            const int k = moves->n_moves;
-            for (int m = 0; m < k; ++m) {
-                const size_t slab = (size_t)(j - 1) * k + m;
-                FAB_TRY(flow_move_impl(a->flow, a->target, a->point, B, a->n_valid, cj, moves->noise_g + slab * B * D,
-                                       moves->noise_h + slab * B, moves->p_accept_out ? moves->p_accept_out + slab : nullptr,
-                                       nullptr, w.mv_word, w.mv_prop, st));
-            }
-        }
-        if (hmc) {
-            fabhip_hmc_args h;
-            h.flow = a->flow; h.target = a->target; h.point = a->point; h.B = B; h.n_valid = a->n_valid;
-            h.cur = cj; h.next = cn; h.log_w = lw;
-            h.noise_p = a->noise_a + nslab * B * D; h.noise_e = a->noise_b + nslab * B;
-            h.epsilons = a->step_state + nslab; h.common_epsilon = a->common_epsilon; h.mass = a->mass;
-            h.n_outer = a->n_inner; h.L = a->L; h.max_grad = a->max_grad; h.target_p_accept = a->target_p_accept;
-            h.tune = a->tune;
-            h.p_accept = nullptr; h.avg_distance = nullptr;
-            h.workspace = w.trans_ws; h.workspace_bytes = w.trans_bytes;
-            h.partials = partials;
-            // logging slots of the first / last distribution (hmc.py:173-183), one acceptance per outer loop
-            if (j == 1) { h.p_accept = a->p_accept_first; h.avg_distance = a->avg_distance_first; }
-            else if (j == a->M) { h.p_accept = a->p_accept_last; h.avg_distance = a->avg_distance_last; }
-            FAB_TRY(hmc_transition_impl(&h, st, ticket, mx));
-        } else {
-            fabhip_metropolis_args m;
-            m.flow = a->flow; m.target = a->target; m.point = a->point; m.B = B; m.n_valid = a->n_valid;
-            m.cur = cj; m.next = cn; m.log_w = lw;
-            m.noise_x = a->noise_a + nslab * B * D; m.noise_u = a->noise_b + nslab * B;
-            m.noise_scalings = a->step_state + nslab; m.n_updates = a->n_inner;
-            m.target_p_accept = a->target_p_accept; m.tune = a->tune;
-            m.workspace = w.trans_ws; m.workspace_bytes = w.trans_bytes;
-            // deferred rule: transition j's block sums + count at slab offset (j - 1) (n_updates nblk + 1)
-            FAB_TRY(metropolis_transition_impl(&m, st, partials ? partials + (size_t)(j - 1) * ((size_t)a->n_inner * nblk_of(B) + 1)
-                                                                 : nullptr, mx));
-        }
-    }
-    // 5. remove nan/inf ("chain end"), 6. ESS / log Z over the survivors (ais.py:77-86)
-    if (do_finish)
-        FAB_TRY(phase_tail(a->point, a->log_w, B, D, a->n_valid, a->n_valid + 1, w.tmp, w.dest, nullptr, nullptr, (double)B,
-                           a->stats + 3, w.ess_ws, w.ess_bytes, nullptr, nullptr, nullptr, st));
-    return check_launch();
 }
 
 }  // extern "C"

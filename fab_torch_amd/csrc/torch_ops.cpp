@@ -763,7 +763,7 @@ void spline_hmc_transition(const Tensor& packed, int64_t dim, int64_t n_layers, 
     chk(fabhip_spline_hmc_transition(&a, stream_of(x)), "spline_hmc_transition");
 }
 
-// What the whole-call AIS ops (ais_run, ais_run_smc, spline_ais_run) and their argument structs have in common.
+// What the whole-call AIS ops (ais_run, ais_run_ext, spline_ais_run) and their argument structs have in common.
 // The four logging slots (hmc.py:173-183, store_info): at least n_inner / 1 floats each.
 template <class Args>
 void fill_logging_slots(Args& a, int64_t n_inner, const Tensor& ref, const optional<Tensor>& p_accept_first,
@@ -904,7 +904,7 @@ struct AisCall {
 };
 
 // flow, target, B / M / betas, alpha / p_target / transition, the operator's step state and settings, the logging slots and the
-// workspace (`smc_on`: with the resampling step's share).  `ref`: the tensor whose device and stream the call is enqueued on.
+// workspace (`ext`: with the share of each mode that is on).  `ref`: the tensor whose device and stream the call is enqueued on.
 void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
                    at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales,
                    at::ArrayRef<double> betas, double alpha, bool p_target, int64_t transition, int64_t B, const Tensor& ref,
@@ -912,7 +912,7 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
                    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune,
                    const optional<Tensor>& p_accept_first, const optional<Tensor>& p_accept_last,
                    const optional<Tensor>& avg_distance_first, const optional<Tensor>& avg_distance_last, int64_t precision,
-                   bool smc_on, bool moves_on = false) {
+                   const fabhip_ais_ext* ext) {
     fabhip_ais_args& a = c.a;
     a.flow = make_flow(packed, dim, n_layers, width, precision);
     a.target = make_target(kind, prm, locs, scales, dim, packed);
@@ -934,9 +934,7 @@ void fill_ais_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_laye
     a.n_inner = (int32_t)n_inner; a.L = (int32_t)L; a.max_grad = (float)max_grad;
     a.target_p_accept = (float)target_p_accept; a.tune = tune ? 1 : 0;
     fill_logging_slots(a, n_inner, ref, p_accept_first, p_accept_last, avg_distance_first, avg_distance_last);
-    const size_t nb = moves_on ? fabhip_ais_moves_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner, smc_on ? 1 : 0)
-                      : smc_on ? fabhip_ais_smc_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner)
-                               : fabhip_ais_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner);
+    const size_t nb = fabhip_ais_ext_workspace_bytes(B, (int32_t)dim, (int32_t)n_inner, ext);
     c.ws = scratch(nb, ref);
     a.workspace = aligned(c.ws); a.workspace_bytes = nb;
 }
@@ -955,16 +953,21 @@ struct MovesOp {
     optional<Tensor> noise_g, noise_h;
     Tensor g, h, p_accept;                              // the draws the call used; out: acceptance fractions [M, k]
 };
-// SMC mode of the AIS ops (fabhip_smc_args): `tau` absent = the plain call through the same entry points.  noise_r [M] float64
-// (absent: drawn from the default generator AFTER the transition noise); the per-transition records are allocated here.
+// SMC mode of the AIS ops (fabhip_smc_args).  noise_r [M] float64 (absent: drawn from the default generator AFTER the transition
+// noise); the per-transition records are allocated here.
 struct SmcOp {
-    optional<double> tau;
+    double tau = 0.0;
     optional<Tensor> noise_r;
     bool want_trace = false;
     int64_t method = 0;                                 // FABHIP_SMC_SYSTEMATIC / FABHIP_SMC_STRATIFIED
-    Tensor resampled, ess, ancestors, log_w_pre, u;     // out (ais_run_smc)
-    const MixOp* mix = nullptr;                         // ais_run_mix: the call goes through fabhip_ais_*_mix
-    MovesOp* moves = nullptr;                           // ais_run_moves: the call goes through fabhip_ais_*_moves
+    Tensor resampled, ess, ancestors, log_w_pre, u;     // out
+};
+// The optional modes of one AIS op call (fabhip_ais_ext), each absent = not named.  The next mode is one more member here and one
+// more parameter group of ais_run_ext.
+struct AisExtOp {
+    optional<SmcOp> smc;
+    optional<MixOp> mix;
+    optional<MovesOp> moves;
 };
 
 fabhip_defensive_args make_mix(const MixOp& m, int64_t dim, const Tensor& ref) {
@@ -983,15 +986,9 @@ static Tensor smc_uniforms(const optional<Tensor>& noise_r, int64_t M, const Ten
     return *noise_r;
 }
 
-// The plain op of an implementation whose first parameter is its SMC mode: the same parameter list without it, NULL passed.
-template <auto Impl> struct Plain;
-template <class R, class S, class... A, R (*Impl)(S*, A...)> struct Plain<Impl> {
-    static R op(A... a) { return Impl(nullptr, std::forward<A>(a)...); }
-};
-
-// `smc` == nullptr: the plain op (ais_run) - the same entry points of the C ABI with a NULL fabhip_smc_args.
+// `ext` == nullptr: the plain op (ais_run) - the entry points of ais_run_ext with a NULL fabhip_ais_ext.
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run_impl(
-    SmcOp* smc, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+    AisExtOp* ext, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
     const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
     bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
     const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
@@ -999,20 +996,29 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
     int64_t precision) {
     c10::DeviceGuard g(eps0.device());
-    const bool smc_on = smc != nullptr && smc->tau.has_value();
+    SmcOp* smc = ext != nullptr && ext->smc.has_value() ? &*ext->smc : nullptr;
+    const MixOp* mix = ext != nullptr && ext->mix.has_value() ? &*ext->mix : nullptr;
+    MovesOp* mv = ext != nullptr && ext->moves.has_value() ? &*ext->moves : nullptr;
     // noise_a / noise_b absent: drawn HERE, from the default generator in the order the Python side draws them (normal
     // [M, n_inner, B, dim], then exponential(1) / uniform [M, n_inner, B]) - but AFTER the chain initialisation is enqueued, so the
     // device works while the host launches the draws (FABHIP_AIS_CONTINUE)
     TORCH_CHECK(noise_a_in.has_value() == noise_b_in.has_value(), "fabhip: pass both noise tensors or neither");
     const bool draw_inside = !noise_a_in.has_value();
     TORCH_CHECK(eps0.dim() == 2 && eps0.size(1) == dim, "fabhip: eps0 must be [B, dim]");
-    MovesOp* mv = smc != nullptr ? smc->moves : nullptr;
-    TORCH_CHECK(mv == nullptr || mv->n_moves >= 0, "fabhip: n_moves must be >= 0");
-    const bool moves_on = mv != nullptr && mv->n_moves > 0;
+    // the C structs of the modes: their switches now (the workspace is sized by them), their tensors where the generator's order
+    // of draws puts them
+    fabhip_smc_args sa = {};                                   // (records: NULL until smc_outputs)
+    fabhip_defensive_args ma = {};
+    fabhip_flow_moves_args fm = {};
+    if (smc != nullptr) { sa.enabled = 1; sa.tau = smc->tau; sa.method = (int32_t)smc->method; }
+    if (mix != nullptr) ma.enabled = mix->enabled ? 1 : 0;
+    if (mv != nullptr) fm.n_moves = (int32_t)mv->n_moves;
+    const fabhip_ais_ext whole = {smc != nullptr ? &sa : nullptr, mix != nullptr ? &ma : nullptr, mv != nullptr ? &fm : nullptr};
+    const fabhip_ais_ext* xp = ext != nullptr ? &whole : nullptr;
     AisCall c;
     fill_ais_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0.size(0), eps0,
                   step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first, p_accept_last,
-                  avg_distance_first, avg_distance_last, precision, smc_on, moves_on);
+                  avg_distance_first, avg_distance_last, precision, xp);
     fabhip_ais_args& a = c.a;
     const int64_t B = c.B, M = c.M;
     const bool hmc = c.hmc;
@@ -1038,10 +1044,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
                            hmc ? gq.data_ptr<float>() : nullptr, hmc ? gp.data_ptr<float>() : nullptr};
     a.log_w = log_w.data_ptr<float>();
     const AisOutputs o = alloc_ais_outputs(a, B, dim, eps0, want_base);
-    fabhip_smc_args sa = {};                                   // (records: NULL until smc_outputs)
-    sa.enabled = smc_on ? 1 : 0; sa.tau = smc_on ? *smc->tau : 0.0; sa.method = smc != nullptr ? (int32_t)smc->method : 0;
     auto smc_outputs = [&]() {                                 // (after the transition noise: the generator's order of draws)
-        if (!smc_on) return;
+        if (smc == nullptr) return;
         smc->u = smc_uniforms(smc->noise_r, M, eps0);
         smc->resampled = at::empty({M}, eps0.options().dtype(at::kInt));
         smc->ess = fempty({M}, eps0);
@@ -1052,97 +1056,96 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
             sa.ancestors = smc->ancestors.data_ptr<int32_t>(); sa.log_w_pre = smc->log_w_pre.data_ptr<float>();
         }
     };
-    const fabhip_smc_args* sap = smc != nullptr ? &sa : nullptr;
-    fabhip_flow_moves_args fm = {};
     auto moves_noise = [&]() {                                 // (behind the transition noise, in front of noise_r)
-        if (!moves_on) return;
+        if (mv == nullptr) return;
         const int64_t k = mv->n_moves;
         TORCH_CHECK(mv->noise_g.has_value() == mv->noise_h.has_value(), "fabhip: pass both noise_g and noise_h or neither");
         mv->g = mv->noise_g.has_value() ? *mv->noise_g : at::randn({M, k, B, dim}, eps0.options());
         mv->h = mv->noise_h.has_value() ? *mv->noise_h : at::empty({M, k, B}, eps0.options()).exponential_(1.0);
         mv->p_accept = fempty({M, k}, eps0);
-        fm.n_moves = (int32_t)k;
         fm.noise_g = fpn(mv->g, M * k * B * dim, eps0, "noise_g"); fm.noise_h = fpn(mv->h, M * k * B, eps0, "noise_h");
         fm.p_accept_out = mv->p_accept.data_ptr<float>();
     };
-    const fabhip_flow_moves_args* fmp = moves_on ? &fm : nullptr;
     const fabhip_stream_t st = stream_of(eps0);
-    // defensive mixture (ais_run_mix): the same entry points with a non-NULL fabhip_defensive_args; `sel` absent: drawn after eps0
-    // (the caller's draw) and before the transition noise
-    fabhip_defensive_args ma = {};
-    const fabhip_defensive_args* map = nullptr;
+    // defensive mixture: `sel` absent: drawn after eps0 (the caller's draw) and before the transition noise
     Tensor sel;
-    if (smc != nullptr && smc->mix != nullptr) {
-        ma = make_mix(*smc->mix, dim, eps0);
-        if (smc->mix->enabled) {
-            sel = smc->mix->sel.has_value() ? *smc->mix->sel : at::rand({B}, eps0.options());
+    if (mix != nullptr) {
+        ma = make_mix(*mix, dim, eps0);
+        if (mix->enabled) {
+            sel = mix->sel.has_value() ? *mix->sel : at::rand({B}, eps0.options());
             ma.sel = fpn(sel, B, eps0, "sel");
         }
-        map = &ma;
     }
-    const char* what = map ? "ais_run_mix" : "ais_run";
+    const bool named = ext != nullptr;
     if (!draw_inside) {
         moves_noise();
         smc_outputs();
-        chk(fabhip_ais_run_moves(&a, sap, map, fmp, st), what);
+        chk(fabhip_ais_run_ext(&a, xp, st), named ? "ais_run_ext" : "ais_run");
     } else {
-        chk(fabhip_ais_phase_moves(&a, sap, map, nullptr, FABHIP_AIS_INIT, 1, 0, nullptr, st),
-            map ? "ais_run_mix (chain initialisation)" : "ais_run (chain initialisation)");
+        chk(fabhip_ais_phase_ext(&a, xp, FABHIP_AIS_INIT, 1, 0, nullptr, st),      // (reads no noise of the transitions or moves)
+            named ? "ais_run_ext (chain initialisation)" : "ais_run (chain initialisation)");
         noise_a = at::randn({M, n_inner, B, dim}, eps0.options());
         noise_b = hmc ? at::empty({M, n_inner, B}, eps0.options()).exponential_(1.0) : at::rand({M, n_inner, B}, eps0.options());
         a.noise_a = noise_a.data_ptr<float>(); a.noise_b = noise_b.data_ptr<float>();
         moves_noise();
         smc_outputs();
-        chk(fabhip_ais_phase_moves(&a, sap, map, fmp, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
-            map ? "ais_run_mix (transitions)" : "ais_run (transitions)");
+        chk(fabhip_ais_phase_ext(&a, xp, FABHIP_AIS_CONTINUE | FABHIP_AIS_FINISH, 1, (int32_t)M, nullptr, st),
+            named ? "ais_run_ext (transitions)" : "ais_run (transitions)");
     }
     return {x, lq, lp, gq, gp, log_w, o.n_valid, o.stats, o.base_x, o.base_lw};
 }
 
-// ais_run with the SMC mode: the ten outputs of ais_run, then resampled int32[M], ess float[M], ancestors int32[M, B],
-// log_w_pre float[M, B] (the last two empty unless want_trace; all four empty when tau is absent).
-std::vector<Tensor> ais_run_smc(
+// The headline op: the whole call without any optional mode.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ais_run(
     const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
     const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
-    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
-    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
-    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, int64_t method) {
-    SmcOp smc;
-    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.method = method;
-    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
-                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
-    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
-    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
-            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
-            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a, const optional<Tensor>& noise_b,
+    Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
+    double target_p_accept, bool tune, optional<Tensor> p_accept_first, optional<Tensor> p_accept_last,
+    optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base, int64_t precision) {
+    return ais_run_impl(nullptr, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                        noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                        p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
 }
 
-// ais_run_smc with n_moves flow-proposal moves in front of every transition (fabhip_ais_run_moves; `tau` absent: plain AIS with
-// moves): the fourteen outputs of ais_run_smc, then the acceptance fractions float[M, n_moves] (empty with n_moves == 0, which
-// is ais_run_smc launch for launch).
-std::vector<Tensor> ais_run_moves(
+// The five outputs the modes add behind the ten of ais_run: resampled int32[M], ess float[M], ancestors int32[M, B], log_w_pre
+// float[M, B] (SMC mode; the last two only with want_trace), the moves' acceptance fractions float[M, n_moves].  Empty where the
+// mode is off.
+static void push_ext_outputs(std::vector<Tensor>& out, const AisExtOp& ext, const Tensor& like) {
+    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, like.options().dtype(ty)); };
+    const SmcOp smc = ext.smc.value_or(SmcOp{});
+    out.push_back(e(smc.resampled, at::kInt)); out.push_back(e(smc.ess, at::kFloat));
+    out.push_back(e(smc.ancestors, at::kInt)); out.push_back(e(smc.log_w_pre, at::kFloat));
+    out.push_back(e(ext.moves.has_value() ? ext.moves->p_accept : Tensor(), at::kFloat));
+}
+
+// ais_run with its optional modes, each named by its parameter group (fabhip_ais_run_ext): SMC mode (`tau` given), the defensive
+// mixture as base distribution (`mix_loc` given; mix_enabled = false: the call without it through the same entry points), n_moves
+// > 0 flow-proposal moves in front of every transition.  Fifteen outputs, always: ais_run's ten, then push_ext_outputs' five.
+std::vector<Tensor> ais_run_ext(
     const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
     const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
-    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
-    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
-    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, int64_t method, int64_t n_moves,
-    const optional<Tensor>& noise_g, const optional<Tensor>& noise_h) {
-    MovesOp mv;
-    mv.n_moves = n_moves; mv.noise_g = noise_g; mv.noise_h = noise_h;
-    SmcOp smc;
-    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.method = method; smc.moves = &mv;
-    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
-                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
-    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
-    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
-            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
-            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat), e(mv.p_accept, at::kFloat)};
+    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a, const optional<Tensor>& noise_b,
+    Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
+    double target_p_accept, bool tune, optional<Tensor> p_accept_first, optional<Tensor> p_accept_last,
+    optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base, int64_t precision,
+    optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, int64_t method, const optional<Tensor>& mix_loc,
+    const optional<Tensor>& mix_log_scale, const optional<Tensor>& mix_logit, const optional<Tensor>& sel, bool mix_enabled,
+    int64_t n_moves, const optional<Tensor>& noise_g, const optional<Tensor>& noise_h) {
+    AisExtOp ext;
+    if (tau.has_value()) ext.smc = SmcOp{*tau, noise_r, want_trace, method};
+    TORCH_CHECK(mix_loc.has_value() == mix_log_scale.has_value() && mix_loc.has_value() == mix_logit.has_value(),
+                "fabhip: pass mix_loc, mix_log_scale and mix_logit together or none of them");
+    if (mix_loc.has_value()) ext.mix = MixOp{mix_enabled, *mix_loc, *mix_log_scale, *mix_logit, sel};
+    TORCH_CHECK(n_moves >= 0, "fabhip: n_moves must be >= 0");
+    if (n_moves > 0) ext.moves = MovesOp{n_moves, noise_g, noise_h};
+    std::vector<Tensor> out = std::apply(
+        [](auto&&... t) { return std::vector<Tensor>{t...}; },
+        ais_run_impl(&ext, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0, noise_a,
+                     noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first,
+                     p_accept_last, avg_distance_first, avg_distance_last, want_base, precision));
+    push_ext_outputs(out, ext, eps0);
+    return out;
 }
 
 // One flow-proposal independence move on Point tensors, in place (fabhip_flow_move): (acceptance fraction float[1], accepted
@@ -1179,30 +1182,6 @@ std::tuple<Tensor, Tensor> flow_move(const Tensor& packed, int64_t dim, int64_t 
     return {frac, count};
 }
 
-// ais_run_smc with the defensive mixture as base distribution (fabhip_ais_run_mix): the fourteen outputs of ais_run_smc.
-// `enabled` = false: the call without the mixture through the same entry points (launch for launch the plain call).
-std::vector<Tensor> ais_run_mix(
-    const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
-    const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha,
-    bool p_target, int64_t transition, const Tensor& eps0, const optional<Tensor>& noise_a_in,
-    const optional<Tensor>& noise_b_in, Tensor step_state, optional<Tensor> common_epsilon, const optional<Tensor>& mass,
-    int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, optional<Tensor> p_accept_first,
-    optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, bool want_base,
-    int64_t precision, optional<double> tau, const optional<Tensor>& noise_r, bool want_trace, const Tensor& loc,
-    const Tensor& log_scale, const Tensor& logit, const optional<Tensor>& sel, bool enabled, int64_t method) {
-    MixOp mix;
-    mix.enabled = enabled; mix.loc = loc; mix.log_scale = log_scale; mix.logit = logit; mix.sel = sel;
-    SmcOp smc;
-    smc.tau = tau; smc.noise_r = noise_r; smc.want_trace = want_trace; smc.mix = &mix; smc.method = method;
-    auto t = ais_run_impl(&smc, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
-                          noise_a_in, noise_b_in, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                          p_accept_first, p_accept_last, avg_distance_first, avg_distance_last, want_base, precision);
-    auto e = [&](const Tensor& v, at::ScalarType ty) { return v.defined() ? v : at::empty({0}, eps0.options().dtype(ty)); };
-    return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
-            std::get<7>(t), std::get<8>(t), std::get<9>(t), e(smc.resampled, at::kInt), e(smc.ess, at::kFloat),
-            e(smc.ancestors, at::kInt), e(smc.log_w_pre, at::kFloat)};
-}
-
 // The mixture's density (and d/dx with with_grad) at x [B, dim]: one launch (fabhip_defensive_log_prob).
 std::tuple<Tensor, Tensor> defensive_log_prob(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, const Tensor& loc,
                                               const Tensor& log_scale, const Tensor& logit, const Tensor& x, bool with_grad,
@@ -1235,11 +1214,12 @@ float* ais_phase_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_l
                       const Tensor& log_w, const Tensor& n_valid, const Tensor& stats, const optional<Tensor>& partials,
                       const optional<Tensor>& p_accept_first, const optional<Tensor>& p_accept_last,
                       const optional<Tensor>& avg_distance_first, const optional<Tensor>& avg_distance_last,
-                      const optional<Tensor>& base_x, const optional<Tensor>& base_log_w, int64_t precision, bool smc_on) {
+                      const optional<Tensor>& base_x, const optional<Tensor>& base_log_w, int64_t precision,
+                      const fabhip_ais_ext* ext) {
     TORCH_CHECK(x.dim() == 2 && x.size(1) == dim, "fabhip: x must be [B, dim]");
     fill_ais_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, x.size(0), x,
                   step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune, p_accept_first, p_accept_last,
-                  avg_distance_first, avg_distance_last, precision, smc_on);
+                  avg_distance_first, avg_distance_last, precision, ext);
     fabhip_ais_args& a = c.a;
     const int64_t B = c.B, M = c.M;
     TORCH_CHECK(!c.hmc || (grad_log_q.has_value() && grad_log_p.has_value()),
@@ -1259,25 +1239,23 @@ float* ais_phase_args(AisCall& c, const Tensor& packed, int64_t dim, int64_t n_l
                                     : fabhip_metropolis_partials_floats(B, (int32_t)M, (int32_t)n_inner), x, "partials");
 }
 
-// ais_phase / ais_phase_smc: the phases and transitions the caller names, once.  `smc` == nullptr: the plain op.
-void ais_phase_core(const fabhip_smc_args* smc, const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind,
-                    at::ArrayRef<double> prm, const optional<Tensor>& locs, const optional<Tensor>& scales,
-                    at::ArrayRef<double> betas, double alpha, bool p_target, int64_t transition, int64_t phases, int64_t j_begin,
-                    int64_t j_end, const optional<Tensor>& eps0, const Tensor& noise_a, const Tensor& noise_b, Tensor step_state,
-                    optional<Tensor> common_epsilon, const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad,
-                    double target_p_accept, bool tune, Tensor x, Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q,
-                    optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid, Tensor stats, optional<Tensor> partials,
-                    optional<Tensor> p_accept_first, optional<Tensor> p_accept_last, optional<Tensor> avg_distance_first,
-                    optional<Tensor> avg_distance_last, optional<Tensor> base_x, optional<Tensor> base_log_w, int64_t precision) {
+// ais_phase: the phases and transitions the caller names, once (fabhip_ais_phase_ext with a NULL fabhip_ais_ext).
+void ais_phase(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t width, int64_t kind, at::ArrayRef<double> prm,
+               const optional<Tensor>& locs, const optional<Tensor>& scales, at::ArrayRef<double> betas, double alpha, bool p_target,
+               int64_t transition, int64_t phases, int64_t j_begin, int64_t j_end, const optional<Tensor>& eps0,
+               const Tensor& noise_a, const Tensor& noise_b, Tensor step_state, optional<Tensor> common_epsilon,
+               const optional<Tensor>& mass, int64_t n_inner, int64_t L, double max_grad, double target_p_accept, bool tune, Tensor x,
+               Tensor log_q, Tensor log_p, optional<Tensor> grad_log_q, optional<Tensor> grad_log_p, Tensor log_w, Tensor n_valid,
+               Tensor stats, optional<Tensor> partials, optional<Tensor> p_accept_first, optional<Tensor> p_accept_last,
+               optional<Tensor> avg_distance_first, optional<Tensor> avg_distance_last, optional<Tensor> base_x,
+               optional<Tensor> base_log_w, int64_t precision) {
     c10::DeviceGuard g(x.device());
     AisCall c;
     float* slab = ais_phase_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
                                  noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
                                  x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first,
-                                 p_accept_last, avg_distance_first, avg_distance_last, base_x, base_log_w, precision,
-                                 smc != nullptr && smc->enabled);
-    chk(fabhip_ais_phase_smc(&c.a, smc, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)),
-        smc != nullptr ? "ais_phase_smc" : "ais_phase");
+                                 p_accept_last, avg_distance_first, avg_distance_last, base_x, base_log_w, precision, nullptr);
+    chk(fabhip_ais_phase_ext(&c.a, nullptr, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)), "ais_phase");
 }
 
 // ais_phase with the SMC mode: transition j's phase starts with its resampling step (`only_resample`: and ends there).  The
@@ -1310,10 +1288,14 @@ void ais_phase_smc(const Tensor& packed, int64_t dim, int64_t n_layers, int64_t 
         sa.ess = fpmn_opt(ess, M, x, "ess");
         sa.log_w_pre = fpmn_opt(log_w_pre, M * B, x, "log_w_pre");
     }
-    ais_phase_core(&sa, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, phases, j_begin,
-                   j_end, eps0, noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
-                   x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first, p_accept_last,
-                   avg_distance_first, avg_distance_last, base_x, base_log_w, precision);
+    c10::DeviceGuard g(x.device());
+    const fabhip_ais_ext ext = {&sa, nullptr, nullptr};
+    AisCall c;
+    float* slab = ais_phase_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
+                                 noise_a, noise_b, step_state, common_epsilon, mass, n_inner, L, max_grad, target_p_accept, tune,
+                                 x, log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first,
+                                 p_accept_last, avg_distance_first, avg_distance_last, base_x, base_log_w, precision, &ext);
+    chk(fabhip_ais_phase_ext(&c.a, &ext, (int32_t)phases, (int32_t)j_begin, (int32_t)j_end, slab, stream_of(x)), "ais_phase_smc");
 }
 
 // The decision of the SMC step alone (fabhip_smc_decide) for samplers that step their transitions from Python:
@@ -1428,7 +1410,7 @@ int64_t ais_sharded_tuned(const Tensor& packed, int64_t dim, int64_t n_layers, i
     float* slab = ais_phase_args(c, packed, dim, n_layers, width, kind, prm, locs, scales, betas, alpha, p_target, transition, eps0,
                                  noise_a, noise_b, step_state, common_epsilon, mass, 1, L, max_grad, target_p_accept, true, x,
                                  log_q, log_p, grad_log_q, grad_log_p, log_w, n_valid, stats, partials, p_accept_first,
-                                 p_accept_last, avg_distance_first, avg_distance_last, c10::nullopt, c10::nullopt, precision, false);
+                                 p_accept_last, avg_distance_first, avg_distance_last, c10::nullopt, c10::nullopt, precision, nullptr);
     const fabhip_ais_args& a = c.a;
     const int64_t B = c.B, M = c.M;
     TORCH_CHECK(c.hmc, "fabhip: ais_sharded_tuned is HMC with n_outer == 1 (the acceptance slab: hmc_partials_floats(B) floats)");
@@ -1677,6 +1659,18 @@ Tensor topk(const Tensor& keys, int64_t k, bool sorted) {
 
 #define TGT "int target_kind, float[] target_params, Tensor? locs, Tensor? scales"
 #define FLW "Tensor packed, int dim, int n_layers, int width"
+// the parameters ais_run / ais_run_ext and ais_phase / ais_phase_smc share, up to and including `int precision`
+#define AIS_RUN FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "                      \
+    "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "         \
+    "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "         \
+    "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision"
+#define AIS_PHASE FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "        \
+    "int j_end, Tensor? eps0, Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, "             \
+    "Tensor? mass, int n_inner, int L, float max_grad, float target_p_accept, bool tune, Tensor(c!) x, "                       \
+    "Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, Tensor(g!)? grad_log_p, Tensor(h!) log_w, "                   \
+    "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "                                 \
+    "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "           \
+    "Tensor(q!)? base_log_w, int precision"
 
 TORCH_LIBRARY(fabhip, m) {
     m.def("abi_version() -> int", abi_version);
@@ -1730,47 +1724,17 @@ TORCH_LIBRARY(fabhip, m) {
     m.def("metropolis_transition(" FLW ", " TGT ", Tensor(a!) x, Tensor(b!) log_q, Tensor(c!) log_p, Tensor(d!)? log_w, "
           "float beta, float beta_next, float alpha, bool p_target, Tensor noise_x, Tensor noise_u, "
           "Tensor(e!) noise_scalings_row, float target_p_accept, bool tune) -> ()");
-    m.def("ais_run(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
-          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
-          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
-          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision=0) -> "
-          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
-
-    m.def("ais_phase(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
-          "int j_end, Tensor? eps0, Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, "
-          "Tensor? mass, int n_inner, int L, float max_grad, float target_p_accept, bool tune, Tensor(c!) x, "
-          "Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, Tensor(g!)? grad_log_p, Tensor(h!) log_w, "
-          "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "
-          "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "
-          "Tensor(q!)? base_log_w, int precision=0) -> ()");
-    m.def("ais_run_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
-          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
-          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
-          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
-          "Tensor? noise_r, bool want_trace, int method=0) -> Tensor[]");
-    m.def("ais_run_mix(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
-          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
-          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
-          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
-          "Tensor? noise_r, bool want_trace, Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor? sel, "
-          "bool enabled=True, int method=0) -> Tensor[]");
-    m.def("ais_run_moves(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, Tensor eps0, "
-          "Tensor? noise_a, Tensor? noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, Tensor? mass, int n_inner, "
-          "int L, float max_grad, float target_p_accept, bool tune, Tensor(c!)? p_accept_first, Tensor(d!)? p_accept_last, "
-          "Tensor(e!)? avg_distance_first, Tensor(f!)? avg_distance_last, bool want_base, int precision, float? tau, "
-          "Tensor? noise_r, bool want_trace, int method, int n_moves, Tensor? noise_g, Tensor? noise_h) -> Tensor[]");
+    m.def("ais_run(" AIS_RUN "=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("ais_phase(" AIS_PHASE "=0) -> ()");
+    m.def("ais_run_ext(" AIS_RUN ", float? tau=None, Tensor? noise_r=None, bool want_trace=False, int method=0, "
+          "Tensor? mix_loc=None, Tensor? mix_log_scale=None, Tensor? mix_logit=None, Tensor? sel=None, bool mix_enabled=False, "
+          "int n_moves=0, Tensor? noise_g=None, Tensor? noise_h=None) -> Tensor[]");
     m.def("flow_move(" FLW ", " TGT ", Tensor(a!) x, Tensor(b!) log_q, Tensor(c!) log_p, Tensor(d!)? grad_log_q, "
           "Tensor(e!)? grad_log_p, Tensor? n_valid, float beta, float alpha, bool p_target, Tensor noise_g, Tensor noise_h, "
           "int precision=0) -> (Tensor, Tensor)");
     m.def("defensive_log_prob(" FLW ", Tensor loc, Tensor log_scale, Tensor mixture_logit, Tensor x, bool with_grad, "
           "int precision=0) -> (Tensor, Tensor)");
-    m.def("ais_phase_smc(" FLW ", " TGT ", float[] betas, float alpha, bool p_target, int transition, int phases, int j_begin, "
-          "int j_end, Tensor? eps0, Tensor noise_a, Tensor noise_b, Tensor(a!) step_state, Tensor(b!)? common_epsilon, "
-          "Tensor? mass, int n_inner, int L, float max_grad, float target_p_accept, bool tune, Tensor(c!) x, "
-          "Tensor(d!) log_q, Tensor(e!) log_p, Tensor(f!)? grad_log_q, Tensor(g!)? grad_log_p, Tensor(h!) log_w, "
-          "Tensor(i!) n_valid, Tensor(j!) stats, Tensor(k!)? partials, Tensor(l!)? p_accept_first, "
-          "Tensor(m!)? p_accept_last, Tensor(n!)? avg_distance_first, Tensor(o!)? avg_distance_last, Tensor(p!)? base_x, "
-          "Tensor(q!)? base_log_w, int precision, float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
+    m.def("ais_phase_smc(" AIS_PHASE ", float? tau, Tensor? noise_r, bool only_resample, Tensor(r!)? resampled, "
           "Tensor(s!)? ess, Tensor(t!)? ancestors, Tensor(u!)? log_w_pre, int method=0) -> ()");
     m.def("smc_decide(Tensor log_w, float tau, Tensor u, int method=0) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("next_beta(Tensor log_w, Tensor log_q, Tensor log_p, Tensor? n_valid, float beta, float alpha, bool p_target, "
@@ -1858,12 +1822,10 @@ TORCH_LIBRARY_IMPL(fabhip, CUDA, m) {      // CUDA == HIP on PyTorch-ROCm; delib
     m.impl("create_point", create_point);
     m.impl("hmc_transition", hmc_transition);
     m.impl("metropolis_transition", metropolis_transition);
-    m.impl("ais_run", Plain<ais_run_impl>::op);
-    m.impl("ais_phase", Plain<ais_phase_core>::op);
-    m.impl("ais_run_smc", ais_run_smc);
+    m.impl("ais_run", ais_run);
+    m.impl("ais_phase", ais_phase);
+    m.impl("ais_run_ext", ais_run_ext);
     m.impl("ais_phase_smc", ais_phase_smc);
-    m.impl("ais_run_mix", ais_run_mix);
-    m.impl("ais_run_moves", ais_run_moves);
     m.impl("flow_move", flow_move);
     m.impl("defensive_log_prob", defensive_log_prob);
     m.impl("smc_decide", smc_decide);

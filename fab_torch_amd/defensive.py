@@ -6,8 +6,8 @@ a base distribution whose density is bounded from below by a Gaussian,
 so that the AIS target p^2 / q stays bounded where the flow's float32 density underflows (defensive importance sampling).
 Parameters under the reference's names, shapes and initial values: `loc [D]` = 0, `log_scale [D]` = 0, `mixture_logit` = 1.
 
-With a fab_torch_amd RealNVP inside, an AIS call over the mixture is ONE fused op (torch.ops.fabhip.ais_run_mix ->
-fabhip_ais_run_mix: the 16-chain kernels' *_mix instantiations read the three parameter tensors directly); operators stepped
+With a fab_torch_amd RealNVP inside, an AIS call over the mixture is ONE fused op (torch.ops.fabhip.ais_run_ext ->
+fabhip_ais_run_ext: the 16-chain kernels' *_mix instantiations read the three parameter tensors directly); operators stepped
 from Python evaluate density + gradient with one launch (`log_prob_and_grad` -> fabhip::defensive_log_prob).  `log_prob` is
 differentiable w.r.t. the flow's and the three mixture parameters: composed in torch on top of the flow's differentiable
 `log_prob`.  Sampling is not differentiable, as in the reference.  Definition of the semantics: tests/defensive_spec.py."""

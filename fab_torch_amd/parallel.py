@@ -138,7 +138,7 @@ def refuse_adaptive(who: str, sampler):
 
 
 def refuse_flow_moves(who: str, sampler):
-    """A flow-proposal move's acceptance fraction and the fused call's moves have no `partials` form (fabhip_ais_phase_moves
+    """A flow-proposal move's acceptance fraction and the fused call's moves have no `partials` form (fabhip_ais_phase_ext
     returns FABHIP_ENOTSUP with sharded chains): the sharded samplers refuse a sampler with `n_flow_moves` set."""
     k = getattr(sampler, "n_flow_moves", 0)
     if k:
@@ -148,8 +148,8 @@ def refuse_flow_moves(who: str, sampler):
 
 
 def refuse_mixture(who: str, sampler):
-    """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_run_mix has no `partials` form and
-    the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
+    """A DefensiveMixtureDistribution base runs through the one-op fused call only (fabhip_ais_phase_ext has no `partials` form
+    for the mixture and the pieces of fabhip_ais_phase would sample the bare flow): the sharded samplers refuse it."""
     from .defensive import DefensiveMixtureDistribution
     if isinstance(getattr(sampler, "base_distribution", None), DefensiveMixtureDistribution):
         from ._ops import FabhipError

@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 225
+#define FABHIP_ABI_VERSION 226
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -623,7 +623,8 @@ int fabhip_ais_phase(const fabhip_ais_args* args, int32_t phases, int32_t j_begi
  *              max + log(sum W 2^-36 / n0), so that logsumexp(log_w) - and with it log Z - is what it was;
  *   else the step is the identity.
  * Decided and executed on the device: the launch sequence does not depend on the outcome, the host never waits.
- * `enabled` == 0 (or a NULL fabhip_smc_args): the plain call, launch for launch.  The outputs may each be NULL.
+ * `enabled` == 0 (or a NULL fabhip_smc_args): the plain call, launch for launch.  The outputs may each be NULL; transition j's
+ * phase writes entry j - 1 of each.  With `partials` (sharded chains): FABHIP_ENOTSUP.  Passed as fabhip_ais_ext.smc (below).
  * `method` = FABHIP_SMC_STRATIFIED: the decision is the same, the ancestors are the stratified resampler's
  * (fabhip_resample_stratified below) for n_samples = n0 and seed = the 64 bits of the float64 u[j - 1] read as an unsigned
  * integer (u outside [0, 1): taken as 0.0, i.e. seed 0) - still one float64 per transition.  Any other value than the two
@@ -644,15 +645,6 @@ typedef struct {
     int32_t method;           /* FABHIP_SMC_SYSTEMATIC (0: what a zero-initialised struct has) or FABHIP_SMC_STRATIFIED          */
 } fabhip_smc_args;
 
-/* fabhip_ais_workspace_bytes + the scratch of the resampling step (CDF, ancestors, flag) */
-size_t fabhip_ais_smc_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner);
-/* fabhip_ais_run / fabhip_ais_phase with the resampling step in front of every transition they run.  Only entry j - 1 of the
- * per-transition outputs is written by transition j's phase.  `partials` (sharded chains) with the mode on: FABHIP_ENOTSUP.
- * Workspace: fabhip_ais_smc_workspace_bytes when the mode is on, fabhip_ais_workspace_bytes otherwise. */
-int fabhip_ais_run_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, fabhip_stream_t stream);
-int fabhip_ais_phase_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc, int32_t phases, int32_t j_begin,
-                         int32_t j_end, float* partials, fabhip_stream_t stream);
-
 /* Defensive-mixture base distribution (fab/trainable_distributions/defensive_mixture.py; definition: tests/defensive_spec.py):
  *   log q(x) = logsumexp(log q_flow(x) + logsigmoid(l), log N(x; loc, exp(log_scale)) + logsigmoid(-l)),   l = logit[0],
  * which bounds the AIS target p^2 / q wherever the Gaussian has mass - also where the flow's float32 density underflows.
@@ -662,7 +654,8 @@ int fabhip_ais_phase_smc(const fabhip_ais_args* args, const fabhip_smc_args* smc
  * The kernels read the three parameter tensors directly (device; no packed copy, no host read).  The mode runs on the 16-chain
  * tiles at every batch size, fp32 only (FABHIP_PRECISION_FAST / the process-wide fast mode: FABHIP_ENOTSUP), not with
  * `partials` (sharded chains: FABHIP_ENOTSUP).  `enabled` == 0 (or a NULL fabhip_defensive_args): the call without the mixture,
- * launch for launch. */
+ * launch for launch.  Composes with the SMC mode (only the point and log_w move in a resampling step); needs no workspace of its
+ * own.  Passed as fabhip_ais_ext.mix (below). */
 typedef struct {
     int32_t enabled;
     const float* loc;         /* device [dim]                                                                       */
@@ -670,12 +663,6 @@ typedef struct {
     const float* logit;       /* device [1]: P(flow branch) = sigmoid(logit)                                        */
     const float* sel;         /* device [B] uniforms in [0, 1): the branch draws; read by FABHIP_AIS_INIT only      */
 } fabhip_defensive_args;
-/* fabhip_ais_run_smc / fabhip_ais_phase_smc with the mixture as base distribution (smc may be NULL; the two modes compose: only
- * the point and log_w move in a resampling step).  Workspace: as for the same call without the mixture. */
-int fabhip_ais_run_mix(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                       fabhip_stream_t stream);
-int fabhip_ais_phase_mix(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                         int32_t phases, int32_t j_begin, int32_t j_end, float* partials, fabhip_stream_t stream);
 /* The mixture's density alone: log_q [B] and, with grad_x != NULL, d log q / dx [B][dim] at x [B][dim] - one launch, for
  * operators stepped from the host.  `mix->sel` is not read.  `workspace`: reserved, may be NULL. */
 int fabhip_defensive_log_prob(const fabhip_flow* flow, const fabhip_defensive_args* mix, const float* x, float* log_q,
@@ -713,20 +700,29 @@ int fabhip_flow_move(const fabhip_flow_move_args* args, fabhip_stream_t stream);
  * (resample, move globally, move locally).  Steps run with smc->only_resample skip the moves.  noise_g / noise_h are read by
  * the transitions only (like noise_a / noise_b); with n_moves > 0 and transitions to run, NULL is FABHIP_EINVAL.  n_moves == 0
  * (or a NULL fabhip_flow_moves_args): the call without moves, launch for launch.  With `partials` (sharded chains) or a
- * defensive mixture: FABHIP_ENOTSUP.  Workspace: fabhip_ais_moves_workspace_bytes (smc != 0: with the resampling step's
- * share), the layout of the call without moves with the proposal buffers behind it. */
+ * defensive mixture: FABHIP_ENOTSUP.  Workspace: the layout of the call without moves with the proposal buffers behind it. */
 typedef struct {
     int32_t n_moves;          /* k >= 0 */
     const float* noise_g;     /* device [M][k][B][dim] ~ N(0,1) */
     const float* noise_h;     /* device [M][k][B] ~ Exp(1) */
     float* p_accept_out;      /* device [M][k] acceptance fractions, or NULL; entry (j - 1, m) is written by step j's phase */
 } fabhip_flow_moves_args;
-size_t fabhip_ais_moves_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, int32_t smc);
-int fabhip_ais_run_moves(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                         const fabhip_flow_moves_args* moves, fabhip_stream_t stream);
-int fabhip_ais_phase_moves(const fabhip_ais_args* args, const fabhip_smc_args* smc, const fabhip_defensive_args* mix,
-                           const fabhip_flow_moves_args* moves, int32_t phases, int32_t j_begin, int32_t j_end,
-                           float* partials, fabhip_stream_t stream);
+
+/* The fused call with its optional modes (ABI 226): SMC resampling, the defensive mixture, flow-proposal moves - each described
+ * at its struct above.  A NULL `ext`, a NULL member, and a member whose own switch is off (`enabled` == 0, `n_moves` == 0) all
+ * mean the call without that mode, launch for launch: fabhip_ais_run(args) == fabhip_ais_run_ext(args, NULL) and
+ * fabhip_ais_phase(args, ..) == fabhip_ais_phase_ext(args, NULL, ..).  Workspace: fabhip_ais_ext_workspace_bytes for the same
+ * `ext` (only the switches are read; with no mode on: fabhip_ais_workspace_bytes); a mode that is on and finds its share
+ * missing: FABHIP_ENOSPC.  The next mode becomes one more member here. */
+typedef struct {
+    const fabhip_smc_args* smc;
+    const fabhip_defensive_args* mix;
+    const fabhip_flow_moves_args* moves;
+} fabhip_ais_ext;
+size_t fabhip_ais_ext_workspace_bytes(int64_t B, int32_t dim, int32_t n_inner, const fabhip_ais_ext* ext);
+int fabhip_ais_run_ext(const fabhip_ais_args* args, const fabhip_ais_ext* ext, fabhip_stream_t stream);
+int fabhip_ais_phase_ext(const fabhip_ais_args* args, const fabhip_ais_ext* ext, int32_t phases, int32_t j_begin, int32_t j_end,
+                         float* partials, fabhip_stream_t stream);
 
 /* The decision alone, for samplers that step their transitions themselves (the generic plug-in path): ancestors [B] (identity
  * where nothing is resampled and beyond *n_ptr rows), resampled [1], log_w_common [1] (the value every log_w[:n0] takes when

@@ -235,23 +235,32 @@ def test_workspace_sizes_are_the_recorded_ones():
     i32, i64 = C.c_int32, C.c_int64
     realnvp = list(itertools.product([1, 15, 16, 17, 1024, 1152, 1153, 2048, 2049, 4096, 32769], [2, 6, 32, 33, 64], [1, 2, 5]))
     spline = [s + (B,) for s, B in itertools.product([(6, 4, 64), (60, 12, 256)], [16, 1000, 2048])]
+
+    def ext_bytes(B, dim, n_inner, smc, moves):        # (only the switches of the modes are read: no device pointer needed)
+        sa, mv = _lib.SmcArgs(enabled=smc), _lib.FlowMovesArgs(n_moves=moves)
+        return lib.fabhip_ais_ext_workspace_bytes(B, dim, n_inner, C.byref(_lib.AisExt(C.pointer(sa), None, C.pointer(mv))))
     spline_ws = [s + (B, g) for s, B, g in itertools.product([(6, 4, 64), (24, 2, 256), (60, 12, 256)], [1, 16, 17, 1000, 2048], [0, 1])]
     grids = {"fabhip_hmc_workspace_bytes": ([i64, i32, i32], realnvp),
              "fabhip_spline_workspace_bytes": ([i32, i32, i32, i64, i32], spline_ws),
              "fabhip_metropolis_workspace_bytes": ([i64, i32, i32], realnvp),
              "fabhip_ais_workspace_bytes": ([i64, i32, i32], realnvp),
-             "fabhip_ais_smc_workspace_bytes": ([i64, i32, i32], realnvp),
+             "fabhip_ais_ext_workspace_bytes": (ext_bytes, [c + m for c in realnvp for m in ((0, 0), (0, 1), (1, 0), (1, 1))]),
              "fabhip_spline_hmc_workspace_bytes": ([i32, i32, i32, i64], spline),
              "fabhip_spline_ais_workspace_bytes": ([i32, i32, i32, i64], spline),
              "fabhip_smc_shard_workspace_bytes": ([i32, i64], list(itertools.product([1, 2, 64], [16, 2048])))}
     assert sorted(rec) == sorted(grids)
     for name, (argtypes, cases) in grids.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = C.c_size_t, argtypes
+        fn = argtypes if callable(argtypes) else getattr(lib, name)
+        if fn is not argtypes:
+            fn.restype, fn.argtypes = C.c_size_t, argtypes
         want = {tuple(r[:-1]): r[-1] for r in rec[name]}
         assert sorted(want) == sorted(cases), f"{name}: the fixture does not hold the cases of this test"
         got = {c: fn(*c) for c in cases}
         assert got == want, {c: (got[c], want[c]) for c in cases if got[c] != want[c]}
+    # no mode on, however it is said, is the plain size
+    for c in realnvp[::7]:
+        assert ext_bytes(*c, 0, 0) == lib.fabhip_ais_ext_workspace_bytes(*c, None) == lib.fabhip_ais_workspace_bytes(*c) == \
+            lib.fabhip_ais_ext_workspace_bytes(*c, C.byref(_lib.AisExt()))
 
 
 def test_spline_image_and_tape_layouts_are_the_recorded_ones():
@@ -274,3 +283,38 @@ def test_spline_image_and_tape_layouts_are_the_recorded_ones():
     for c in cases:
         assert lib.fabhip_spline_tape_layout(*c, lay) == 0
         assert list(lay) == want[c], (c, list(lay), want[c])
+
+
+def test_ais_ext_struct_is_three_pointers_in_the_header_order():
+    """fabhip_ais_ext (no fabhip_abi_sizes slot: three pointers, no padding to disagree on) against the ctypes mirror."""
+    txt = open(os.path.join(ROOT, "include", "fabhip.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\} fabhip_ais_ext;", txt).group(1)
+    fields = re.findall(r"const (fabhip_\w+)\* (\w+);", body)
+    assert fields == [("fabhip_smc_args", "smc"), ("fabhip_defensive_args", "mix"), ("fabhip_flow_moves_args", "moves")]
+    assert [n for n, _ in _lib.AisExt._fields_] == [n for _, n in fields]
+    assert [t._type_ for _, t in _lib.AisExt._fields_] == [_lib.SmcArgs, _lib.DefensiveArgs, _lib.FlowMovesArgs]
+    assert C.sizeof(_lib.AisExt) == 3 * C.sizeof(C.c_void_p)
+
+
+def test_ais_run_ext_wants_the_share_of_every_mode_that_is_on_without_gpu():
+    """fabhip_ais_run_ext on a workspace of fabhip_ais_workspace_bytes: FABHIP_ENOSPC with the SMC mode on and with one move, before
+    anything is enqueued (the argument checks in front of the size check compare pointers with NULL only, so placeholders do).  A
+    member that is present but off asks for nothing more: its size is the plain one here; the call itself runs in
+    tests/test_gpu_ais_ext.py, since a call that passes the size check goes on to launch."""
+    lib = _lib.load()
+    B, D, M, n_inner, ENOSPC = 37, 6, 3, 2, -4
+    some = 0x10000                                         # (never dereferenced: the call returns at the size check)
+    a = _lib.AisArgs()
+    a.flow = _lib.Flow(D, 3, 30, some)
+    a.target = _lib.Target(_lib.TARGET_MANYWELL, D, -1.0, -6.0, 1.0, 0.0, 0, None, None)
+    betas = (C.c_double * (M + 2))(0.0, 0.25, 0.5, 0.75, 1.0)
+    a.B, a.M, a.betas, a.alpha, a.p_target, a.transition = B, M, betas, 2.0, 0, _lib.TRANSITION_HMC
+    a.eps0 = a.noise_a = a.noise_b = a.step_state = a.common_epsilon = a.mass = a.log_w = a.n_valid = a.stats = some
+    a.n_inner, a.L, a.max_grad, a.target_p_accept, a.tune = n_inner, 3, 1e3, 0.65, 1
+    a.point = _lib.Point(some, some, some, some, some)
+    a.workspace, a.workspace_bytes = some, lib.fabhip_ais_workspace_bytes(B, D, n_inner)
+    smc, mv = _lib.SmcArgs(enabled=1, u=some), _lib.FlowMovesArgs(1, some, some, None)
+    assert lib.fabhip_ais_run_ext(C.byref(a), C.byref(_lib.AisExt(C.pointer(smc), None, None)), None) == ENOSPC
+    assert lib.fabhip_ais_run_ext(C.byref(a), C.byref(_lib.AisExt(None, None, C.pointer(mv))), None) == ENOSPC
+    off = _lib.AisExt(C.pointer(_lib.SmcArgs(enabled=0)), C.pointer(_lib.DefensiveArgs(enabled=0)), C.pointer(_lib.FlowMovesArgs(0)))
+    assert lib.fabhip_ais_ext_workspace_bytes(B, D, n_inner, C.byref(off)) == a.workspace_bytes

@@ -226,7 +226,7 @@ def test_mixture_off_is_the_plain_call_and_no_state_leaks(hmc):
         kind, slots = fa.ais.operator_slots(op)
         head = ais._call_head(flow, ais._native_parts()[1], kind)
         if through_mix_op:
-            out = ops.ais_run_mix(*head, eps0, na, nb, *slots, True, 0, None, None, False, *mix.mix_args(), None, False)
+            out = ops.ais_run_ext(*head, eps0, na, nb, *slots, True, 0, None, None, False, 0, *mix.mix_args(), None, False)
             assert all(t.numel() == 0 for t in out[10:])
             out = out[:10]
         else:
@@ -237,7 +237,7 @@ def test_mixture_off_is_the_plain_call_and_no_state_leaks(hmc):
     with _ops.option(_ops.OPT_TILE_SHAPE, 16):
         a, sa = plain_call(False)
         b, sb = plain_call(True)
-    assert all(torch.equal(u, v) for u, v in zip(a, b)), "ais_run_mix with enabled = 0 differs from ais_run"
+    assert all(torch.equal(u, v) for u, v in zip(a, b)), "ais_run_ext with mix_enabled = False differs from ais_run"
     assert all(torch.equal(u, v) for u, v in zip(sa, sb))
     # a plain sampler's result before and after a mixture call on the same flow (default tile choice: 4-chain tiles at B = 40)
     before, s0 = plain_call(False)
@@ -378,7 +378,7 @@ def test_trainer_eval_and_refusals(tmp_path):
             ops = _ops.load()
             kind, slots = fa.ais.operator_slots(ais.transition_operator)
             head = ais._call_head(mix.flow, ais._native_parts()[1], kind)
-            ops.ais_run_mix(*head, torch.randn(64, D, device=DEV), None, None, *slots, False, _ops.PRECISION_FAST, None, None,
-                            False, *mix.mix_args(), None, True)
+            ops.ais_run_ext(*head, torch.randn(64, D, device=DEV), None, None, *slots, False, _ops.PRECISION_FAST, None, None,
+                            False, 0, *mix.mix_args(), None, True)
     finally:
         mix.flow.precision = None

@@ -494,9 +494,14 @@ def test_c_entry_refuses_partials_a_mixture_and_null_noise():
     nv, st = torch.zeros(2, dtype=torch.int32, device=DEV), torch.zeros(16, **F32)
     a.point = _lib.Point(x.data_ptr(), lq.data_ptr(), lp.data_ptr(), gq.data_ptr(), gp.data_ptr())
     a.log_w, a.n_valid, a.stats = lw.data_ptr(), nv.data_ptr(), st.data_ptr()
-    nbytes = lib.fabhip_ais_moves_workspace_bytes(B, D, 1, 0)
+    def ext(smc=None, mix=None, moves=None):                  # fabhip_ais_ext over the members given (the rest NULL)
+        return C.byref(_lib.AisExt(*(None if m is None else C.pointer(m) for m in (smc, mix, moves))))
+
+    on, k1 = _lib.SmcArgs(enabled=1), _lib.FlowMovesArgs(n_moves=1)
+    nbytes = lib.fabhip_ais_ext_workspace_bytes(B, D, 1, ext(moves=k1))
     assert nbytes >= lib.fabhip_ais_workspace_bytes(B, D, 1) + B * (3 * D + 2) * 4
-    assert lib.fabhip_ais_moves_workspace_bytes(B, D, 1, 1) >= lib.fabhip_ais_smc_workspace_bytes(B, D, 1) + B * (3 * D + 2) * 4
+    assert lib.fabhip_ais_ext_workspace_bytes(B, D, 1, ext(smc=on, moves=k1)) >= \
+        lib.fabhip_ais_ext_workspace_bytes(B, D, 1, ext(smc=on)) + B * (3 * D + 2) * 4
     assert lib.fabhip_flow_move_workspace_bytes(B, D) >= B * (3 * D + 2) * 4
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=DEV)
     a.workspace, a.workspace_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
@@ -506,30 +511,29 @@ def test_c_entry_refuses_partials_a_mixture_and_null_noise():
     slab = torch.zeros(int(lib.fabhip_hmc_partials_floats(B)), **F32)
     EINVAL, ENOTSUP, ENOSPC = -1, -2, -4
     # sharded chains
-    assert lib.fabhip_ais_phase_moves(C.byref(a), None, None, C.byref(mv), 0, 1, 1, _lib.ptr(slab), stream) == ENOTSUP
+    assert lib.fabhip_ais_phase_ext(C.byref(a), ext(moves=mv), 0, 1, 1, _lib.ptr(slab), stream) == ENOTSUP
     # a defensive mixture
     loc, ls, logit, sel = torch.zeros(D, **F32), torch.zeros(D, **F32), torch.zeros(1, **F32), torch.rand(B, **F32)
     mix = _lib.DefensiveArgs(1, loc.data_ptr(), ls.data_ptr(), logit.data_ptr(), sel.data_ptr())
-    assert lib.fabhip_ais_run_moves(C.byref(a), None, C.byref(mix), C.byref(mv), stream) == ENOTSUP
+    assert lib.fabhip_ais_run_ext(C.byref(a), ext(mix=mix, moves=mv), stream) == ENOTSUP
     # null noise with moves to run, a negative count, a workspace without the proposal buffers
     for g_ptr, h_ptr in ((None, nh.data_ptr()), (ng.data_ptr(), None)):
-        assert lib.fabhip_ais_run_moves(C.byref(a), None, None, C.byref(_lib.FlowMovesArgs(k, g_ptr, h_ptr, None)), stream) == EINVAL
-    assert lib.fabhip_ais_run_moves(C.byref(a), None, None, C.byref(_lib.FlowMovesArgs(-1, ng.data_ptr(), nh.data_ptr(), None)),
-                                    stream) == EINVAL
+        assert lib.fabhip_ais_run_ext(C.byref(a), ext(moves=_lib.FlowMovesArgs(k, g_ptr, h_ptr, None)), stream) == EINVAL
+    assert lib.fabhip_ais_run_ext(C.byref(a), ext(moves=_lib.FlowMovesArgs(-1, ng.data_ptr(), nh.data_ptr(), None)), stream) == EINVAL
     a.workspace_bytes = lib.fabhip_ais_workspace_bytes(B, D, 1)
-    assert lib.fabhip_ais_run_moves(C.byref(a), None, None, C.byref(mv), stream) == ENOSPC
+    assert lib.fabhip_ais_run_ext(C.byref(a), ext(moves=mv), stream) == ENOSPC
     a.workspace_bytes = nbytes
     torch.cuda.synchronize()
     assert bool((fracs == -1).all())                          # nothing ran
     # and the call itself through the C ABI equals the op
-    _lib.check(lib.fabhip_ais_run_moves(C.byref(a), None, None, C.byref(mv), stream), "ais_run_moves")
+    _lib.check(lib.fabhip_ais_run_ext(C.byref(a), ext(moves=mv), stream), "ais_run_ext")
     pt, log_w, n_valid, stats, _, _ = ais.run(B, eps0, na, nb, noise_g=ng, noise_h=nh)
     assert torch.equal(nv, n_valid) and torch.equal(pt.x, x) and torch.equal(log_w, lw) and torch.equal(ais.last_flow_moves, fracs)
     assert torch.equal(op.epsilons, eps_c)
-    # n_moves = 0 through the new entry is the plain call
+    # n_moves = 0 through the same entry is the plain call
     x0, lw0 = x.clone(), lw.clone()
     eps_c.copy_(_sampler(NARROW)[2].epsilons); ceps_c.copy_(_sampler(NARROW)[2].common_epsilon)
-    _lib.check(lib.fabhip_ais_run_moves(C.byref(a), None, None, C.byref(_lib.FlowMovesArgs(0, None, None, None)), stream), "k = 0")
+    _lib.check(lib.fabhip_ais_run_ext(C.byref(a), ext(moves=_lib.FlowMovesArgs(0, None, None, None)), stream), "k = 0")
     x1, lw1 = x.clone(), lw.clone()
     eps_c.copy_(_sampler(NARROW)[2].epsilons); ceps_c.copy_(_sampler(NARROW)[2].common_epsilon)
     _lib.check(lib.fabhip_ais_run(C.byref(a), stream), "ais_run")

@@ -227,7 +227,7 @@ def test_whole_fused_call_against_the_oracle(D, K, nodes, B, tile):
 
 
 def test_call_in_pieces_and_smc_mode_fill_the_same_mass_fields():
-    """new_phase_state / enqueue_phase (fabhip_ais_phase) and SMC mode with a threshold that never resamples (fabhip_ais_run_smc)
+    """new_phase_state / enqueue_phase (fabhip_ais_phase) and SMC mode with a threshold that never resamples (fabhip_ais_run_ext)
     copy mass and max_grad from their own arguments: bit-identical to the fused call, tuning on."""
     D, K, nodes, B = mc.CHAIN_SHAPES[0]
     c = mc.chain_case(D, K, nodes, B)
@@ -363,7 +363,7 @@ def test_spline_flow_host_fused_and_stepwise(monkeypatch):
 
 # ---- (g) the defensive mixture --------------------------------------------------------------------------------------------------
 def test_defensive_mixture_call_carries_the_mass():
-    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_mix, against defensive_spec's call with
+    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_ext, against defensive_spec's call with
     an oracle HMC that carries the mass and max_grad."""
     D, K, nodes, B = mc.MIX_SHAPE
     c = mc.chain_case(D, K, nodes, B, mix=True)

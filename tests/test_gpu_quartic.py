@@ -218,7 +218,7 @@ def test_whole_fused_call_against_the_oracle(shape, tile):
 
 
 def test_defensive_mixture_call():
-    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_mix"""
+    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_ext"""
     shape = qc.MIX_SHAPE
     c = qc.chain_case(*shape, mix=True)
     hmc, ais = chain_samplers(c, shape, mix=True)

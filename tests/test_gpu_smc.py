@@ -136,7 +136,7 @@ def test_threshold_none_through_the_new_ops_is_bit_identical(hmc):
     for smc in (False, True):
         _, hf, target, op, ais = samplers(hmc=hmc, eval_mode=False)
         ops = _ops.load()
-        call = ops.ais_run_smc if smc else ops.ais_run
+        call = ops.ais_run_ext if smc else ops.ais_run
         extra = (None, None, False) if smc else ()
         if hmc:
             o = call(*hf.native(), *target.native_target(), ais._betas(), 2.0, False, _ops.TRANSITION_HMC, eps0.to(DEV), na.to(DEV),

@@ -100,7 +100,7 @@ def test_systematic_through_the_new_argument_is_bit_identical(hmc):
             ops = _ops.load()
             slots = ((op.epsilons, op.common_epsilon, op.mass_vector, 1, base.L, float(op.max_grad), float(op.target_p_accept), True)
                      if hmc else (op.noise_scalings, None, None, 2, 0, 0.0, float(op.target_prob_accept), True))
-            o = ops.ais_run_smc(*hf.native(), *target.native_target(), ais._betas(), 2.0, False,
+            o = ops.ais_run_ext(*hf.native(), *target.native_target(), ais._betas(), 2.0, False,
                                 _ops.TRANSITION_HMC if hmc else _ops.TRANSITION_METROPOLIS, *dev(eps0, na, nb), *slots,
                                 None, None, None, None, False, 0, TAU_MID, nr.to(DEV), True)
             out = (o[0], o[1], o[2], o[5], o[6], o[7][:6], *o[10:14])

@@ -340,7 +340,7 @@ def test_whole_fused_call_with_the_gmm_against_the_oracle(shape, tile):
 
 
 def test_defensive_mixture_call_with_the_gmm():
-    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_mix"""
+    """k_hmc_step_mix (the MIX instantiation of the 16-chain body) through fabhip::ais_run_ext"""
     shape = tc.MIX_SHAPE
     c = tc.chain_case(*shape, mix=True)
     hmc, ais = chain_samplers(c, shape, mix=True)
