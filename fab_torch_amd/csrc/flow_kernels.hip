@@ -638,9 +638,13 @@ __global__ __launch_bounds__(256) void k_pack_r4f(FlowDims f, R4Dims rd, float* 
             long src = -1;                                 // float4 index inside the layer's r4 block
             const int lsrc = layer < K ? layer : K - 1;    // (virtual sampling layer K has no coupling block)
             const bool coupling = sec != 2 || layer < K;
+            // density sections of the fp32 image: the products into the hidden width are N-split (flow_r4f.h) - the same values,
+            // lane quarter Q of every wave holding what wave Q holds in the K-split tile, for the wave's own 16 G columns
+            const bool nsplit = !fast && sec != 2;
             if (I < 2) {                                   // S1: k-quad 2 w + I of the fused first Linear | S4: of W3^T
-                const int q = 2 * w + I, n = 64 * g + lane;
-                if (sec == 1) src = rd.o_W3T / 4 + ((long)q * G + g) * 64 + lane;
+                int q = 2 * w + I, n = 64 * g + lane;
+                if (nsplit) r4f_nsplit_kn(G, I, w, g, lane, q, n);
+                if (sec == 1) src = rd.o_W3T / 4 + ((long)q * G + (n >> 6)) * 64 + (n & 63);
                 else if (coupling) {
                     for (int j = 0; j < 4; ++j) {
                         const int k = 4 * q + j;
@@ -661,7 +665,9 @@ __global__ __launch_bounds__(256) void k_pack_r4f(FlowDims f, R4Dims rd, float* 
                 }
             } else if (I < I_N) {                          // W x W: k-quad 4 G w + (I - 3)   (fast: k-quads 4 G w + 2 (I - 3), + 1 as bf16)
                 if (!fast) {
-                    if (coupling) src = (sec == 1 ? rd.o_W2T : rd.o_W2) / 4 + ((long)(4 * G * w + (I - 3)) * G + g) * 64 + lane;
+                    int q = 4 * G * w + (I - 3), n = 64 * g + lane;
+                    if (nsplit) r4f_nsplit_kn(G, I, w, g, lane, q, n);
+                    if (coupling) src = (sec == 1 ? rd.o_W2T : rd.o_W2) / 4 + ((long)q * G + (n >> 6)) * 64 + (n & 63);
                 } else {
                     const long b4 = (long)lsrc * LS4 + (sec == 1 ? rd.o_W2T : rd.o_W2) / 4;
                     const int q0 = 4 * G * w + 2 * (I - 3);

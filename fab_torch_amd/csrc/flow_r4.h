@@ -85,6 +85,25 @@ FAB_HD R4Lds make_r4_lds(const FlowDims& f, bool fused = false) {
         // its own reads of the buffer (its epilogue two stages back precedes it in program order, and r4_barrier waits for
         // the wave's LDS reads before it signals).  PZ (narrow partials) needs no second copy: its readers and its next
         // writers are always a barrier apart (S1's z is read in front of S2's barrier and written again behind it, in S3).
+        // (That is the K-split schedule: the sampling direction and fast mode.)
+        //
+        // N-split schedule (density direction, fp32: r4f_short_mma_ns / r4f_dense_wide_ns) - barriers per layer: S1 END, S3 x 2;
+        // S4 END, S6 x 2; S2 / S5 none.  Buffer by buffer, "B(Sn)" = a barrier of stage n:
+        //  HA    written by S1 / S4 (each wave its own 16 G columns) in front of B(S1) / B(S4), read by EVERY wave in S2 / S5 behind
+        //        it; written again in the next layer's S1 / S4, behind both B(S3) / B(S6), which every wave reaches after its S2 / S5.
+        //  HB    written by S2 / S5 (own columns) and read by S3 / S6 (own K range = the same columns) of the SAME wave only:
+        //        r4_wave_handover orders them, no other wave ever touches those columns.
+        //  X     read by every wave at the top of S1 (and of S6), in front of B(S1) (the first B(S6)); written behind that barrier
+        //        (S1: z, by waves 0 / 1; S6: the gradient); read and written by wave 0 in S3's epilogue, behind the first B(S3),
+        //        which waves 0 / 1 reach after their writes; the next S1 / S6 reads it behind the second B(S3) / B(S6).
+        //  DP    read by every wave at the top of S4, in front of B(S4); written in S6's epilogue behind the first B(S6) and read
+        //        again behind the second.
+        //  PART  holds S1's z partials (nothing else in this direction): written in front of B(S1), read by waves 0 / 1 behind it,
+        //        written again in the next layer's S1, behind B(S3).  NOT in PZ: S2 has no barrier, so a wave that runs ahead
+        //        stores its S3 partials to PZ while waves 0 / 1 may still be reading S1's z partials.
+        //  PZ    S3 / S6 only: written in front of the stage's first barrier, read between its two barriers.
+        //  MASK  one word per thread, written (S1, S2) and read (S5, S4) by that thread alone.
+        //  PART2 unused.  (The plan keeps both buffers: the K-split schedule of the other direction and of fast mode needs them.)
         l.o_PART2 = o; o += NWAVE * R4 * l.PN;
         l.o_PZ = o; o += 2 * NWAVE * R4 * 32;
         l.o_BIAS = o; o += (f.K + 1) * r4f_bias_stride(f.Wp);
@@ -351,6 +370,47 @@ __device__ __forceinline__ void r4_epilogue_rf(const float* __restrict__ part, c
 // the hand-over inside the wave: LDS executes a wave's accesses in order; the wait (and the "memory" clobber, for the
 // compiler) puts this wave's output writes in front of its own reads of them in the next stage
 __device__ __forceinline__ void r4_wave_handover() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// ---- N-split products into the hidden width (fused stages, density direction, fp32: flow_r4f.h).  The 16 blocks of a
+// v_mfma_f32_4x4x1 are independent outer products, so each may multiply its own k: lane quarter Q = lane >> 4 of EVERY wave runs the
+// K range that wave Q runs in the K-split form - same tiles' values, same dependent MFMA order from a zero start - for the 16 G
+// columns its wave owns (tile i, lane l: column 16 G w + 16 i + (l & 15); r4f_nsplit_map.h).  Quarter Q of acc[i] then holds, bit
+// for bit, the partial P_Q that wave Q stored to PART, and the four are added inside the wave in the epilogue's order,
+// (P0 + P1) + (P2 + P3): v_permlane16_swap(a, b) leaves [a0 b0 a2 b2] / [a1 b1 a3 b3] (quarters of a, b), whose sum is
+// [a0 + a1, b0 + b1, a2 + a3, b2 + b3]; v_permlane32_swap of two such sums leaves [lower | lower] / [upper | upper], whose sum is
+// the total of row 0, 1, 2, 3 (accumulator registers x, y, z, w) in quarter 0, 1, 2, 3.  Afterwards lane l holds output
+// (row l >> 4, column 16 G w + 16 i + (l & 15)): no partial sums through LDS, no "partials visible" barrier.  (flow_r8.h's fifth
+// column group adds (q0 + q2) + (q1 + q3): not the order wanted here.)  The accumulators must sit in architectural VGPRs
+// (_build.py: -amdgpu-mfma-vgpr-form).
+__device__ __forceinline__ float r4_quarter_sum(const f32x4& a) {
+    const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[0]), __float_as_uint(a[1]), false, false);
+    const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[2]), __float_as_uint(a[3]), false, false);
+    const float s01 = __uint_as_float(p[0]) + __uint_as_float(p[1]);       // rows 0 | 1 | 0 | 1: P0 + P1, P0 + P1, P2 + P3, P2 + P3
+    const float s23 = __uint_as_float(q[0]) + __uint_as_float(q[1]);       // rows 2 | 3 | 2 | 3
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s01), __float_as_uint(s23), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);                  // (P0 + P1) + (P2 + P3) of row lane >> 4
+}
+template <int G>
+__device__ __forceinline__ void r4_bias_ns(float (&bv)[G], const float* __restrict__ b, const Tid4& t) {
+#pragma unroll
+    for (int i = 0; i < G; ++i) bv[i] = b[16 * G * t.wave + 16 * i + (t.lane & 15)];
+}
+// The writes (leading dimension Wp + 16 = 16 mod 64) hit 64 different banks: 16 row + (l & 15) + const.  ReLU sign words per
+// thread as in r4_epilogue_rf (mask[tid], bit i): S1, S2, S4 and S5 of the density direction all use THIS lane-to-output mapping.
+template <int G, int EP>
+__device__ __forceinline__ void r4_epilogue_ns(const f32x4 (&acc)[G], const float (&bv)[G], float* __restrict__ out, int ldo,
+                                               unsigned* mask, const Tid4& t) {
+    unsigned m = EP == 2 ? mask[t.tid] : 0u;
+    const int row = t.lane >> 4, col0 = 16 * G * t.wave + (t.lane & 15);
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        float w = r4_quarter_sum(acc[i]) + bv[i];
+        if (EP == 1) { const bool pos = w > 0.f; m |= (pos ? 1u : 0u) << i; w = pos ? w : 0.f; }
+        if (EP == 2) w = ((m >> i) & 1u) ? w : 0.f;
+        out[row * ldo + col0 + 16 * i] = w;
+    }
+    if (EP == 1) mask[t.tid] = m;
+}
 
 // OUT[4][64 G] = epilogue(ACT[4][Wp] @ B)   (two workgroup barriers: partials visible / outputs visible).
 // `bv`: the bias of this thread's outputs, already in registers (r4_bias_load one W x W stage earlier).

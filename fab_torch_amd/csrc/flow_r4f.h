@@ -14,7 +14,8 @@
 //  the first Linear of layer v the same way (virtual layers 0 .. K: layer 0 starts from the identity, layer K is the last
 //  affine map alone).
 //
-// Arithmetic: the stage sums are the 4-chain tiles' (K split over the 4 waves, partial sums added in a fixed order); h1 differs
+// Arithmetic: the stage sums are the 4-chain tiles' (K split in four, over the waves or - density direction, fp32 - over the lane
+// quarters of every wave; partial sums added in the same fixed order either way, bit for bit); h1 differs
 // from flow_r4.h's by the rounding of W1' (one fp32 rounding of a float64 product instead of two fp32 GEMM stages) - results
 // agree to ~1e-6 relative, not bit for bit (tests/test_gpu_hmc_shapes.py pins the two against each other and the oracle).
 //
@@ -26,11 +27,16 @@
 //    item 3 ..   G tiles each   S2: 4 G k-quads of W2                                | S5: 4 G k-quads of W2^T
 //    last two    G tiles each   S3: 2 G dense tiles of W3 (2 k-quads x 32 columns)   | S6: 2 G dense tiles of W1'^T
 // float4 index of (layer slot s, item I, wave w, tile g, lane): ((s TL + toff(I)) 4 + w ntiles(I) + g) 64 + lane.
+// The table above is the K-split tile (lane = column 64 g + lane, one k-quad per tile and wave): the sampling section and the bf16
+// image.  In the DENSITY sections of the fp32 image the tiles of items 0, 1 and 3 .. are N-split (r4f_nsplit_map.h): the same item
+// pattern, tile counts and bytes, but lane quarter Q of tile g of wave w holds wave Q's k-quad of that item for columns
+// 16 G w + 16 g .. + 15 - the four partial sums of an output end up in the four lane quarters of ONE wave and are added there.
 // Biases / log-dets of all layers live in LDS for the whole kernel (r4f_load_bias: one copy per launch, no bias loads in the
 // layer bodies).
 #pragma once
 #include "flow_r4.h"
 #include "stream_r8.h"
+#include "r4f_nsplit_map.h"
 
 namespace fab {
 
@@ -376,6 +382,69 @@ __device__ __forceinline__ void r4f_dense_wide(const float* act, int lda, Ring& 
     r4_wave_handover();                // (no second barrier: the next stage reads this wave's own columns of `out`)
 }
 
+// ---- N-split forms of S1 / S4 and S2 / S5 (density direction, fp32 image; r4_quarter_sum in flow_r4.h has the argument): lane
+// quarter Q = lane >> 4 of every wave multiplies the k-quads wave Q multiplies above - the same items in the same order, the
+// tiles re-laid by k_pack_r4f (r4f_nsplit_map.h) - for the 16 G columns this wave owns, and the four quarters are added inside
+// the wave.  Same ring, same slots, same waits; no PART round trip.
+// S1 / S4: a0, a1 = ACT[arow][8 Q .. 8 Q + 7]; leaves quarter Q's partial of the own columns in acc0
+template <int NTWM, int I0, class Ring>
+__device__ __forceinline__ void r4f_short_mma_ns(const float4& a0, const float4& a1, Ring& ring, f32x4 (&acc0)[NTWM]) {
+    constexpr int G = NTWM;
+    f32x4 acc1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) { acc0[g] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1[g] = acc0[g]; }
+    ring.wait(IC<I0>{});
+    r4_quad<G>(a0, ring.r[ring.slot(IC<I0>{})], acc0);
+    ring.refill(IC<I0>{});
+    __builtin_amdgcn_sched_barrier(0);
+    ring.wait(IC<I0 + 1>{});
+    r4_quad<G>(a1, ring.r[ring.slot(IC<I0 + 1>{})], acc1);
+    ring.refill(IC<I0 + 1>{});
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc0[g] += acc1[g];
+}
+
+// S2 / S5: reads ALL of `act` (the caller's barrier made it visible), writes this wave's own 16 G columns of `out` - which is all
+// that this wave's K range of S3 / S6 reads (r4f_narrow_mma), so the stage ends with the hand-over inside the wave and has no
+// workgroup barrier at all.  The A read has 16 distinct float4 addresses per instruction (4 rows x 4 quarters) where the K-split
+// form has 4: with lda = Wp + 16 a 4-way bank conflict, issued among the 4 G MFMAs of a k-quad.
+template <int NTWM, int EP, class Ring>
+__device__ __forceinline__ void r4f_dense_wide_ns(const float* act, int lda, Ring& ring, const float* __restrict__ bias, float* out,
+                                                  int ldo, unsigned* mask, const Tid4& t) {
+    using S = typename Ring::S;
+    constexpr int G = NTWM, NQ = 4 * NTWM, I0 = S::I_W;
+    f32x4 acc[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* arow = act + t.arow * lda + 16 * NTWM * (t.lane >> 4);
+    float4 ws[2][G];                   // stash tiles out of LDS, read one item ahead of their MFMAs
+    static_for<0, NQ>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const float4 a = *reinterpret_cast<const float4*>(arow + 4 * q);
+        if constexpr (S::is_stash(I0 + q)) {
+            r4_quad<G>(a, ws[S::stash_k(I0 + q) & 1], acc);
+        } else {
+            ring.wait(IC<I0 + q>{});
+            r4_quad<G>(a, ring.r[ring.slot(IC<I0 + q>{})], acc);
+        }
+        ring.refill(IC<I0 + q>{});
+        if constexpr (q + 1 < NQ && S::is_stash(I0 + q + 1)) {
+            ring.wait_stash(IC<I0 + q + 1>{});
+            ring.read_stash(IC<I0 + q + 1>{}, ws[S::stash_k(I0 + q + 1) & 1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    float bv[G];
+    if (bias) r4_bias_ns<G>(bv, bias, t);
+    else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) bv[g] = 0.f;
+    }
+    r4_epilogue_ns<G, EP>(acc, bv, out, ldo, mask, t);
+    r4_wave_handover();
+}
+
 // the same stage in FAST mode: item i = k-quads 2 i, 2 i + 1 of this wave as bf16 tiles; the activations are rounded to bf16 as
 // they are fetched (v_cvt_pk_bf16_f32, round to nearest even: what fast mode's 16-chain kernels do), one
 // v_mfma_f32_4x4x4_16b_bf16 per k-quad and column group (fp32 accumulation; even / odd quads on separate accumulators, added at
@@ -528,6 +597,11 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
     const int row = t.tid >> 4, c = t.tid & 15;            // element-wise mapping of wave 0 (coupling, base distribution)
     const int zrow = t.tid >> 5, zc = t.tid & 31;          // (row, column) of the 4 x 32 outputs of a dense narrow product
     const int sblk = t.lane >> 5;
+    // Products into the hidden width (S1, S2, S4, S5).  FAST: K split over the waves, partial sums through PART / PART2
+    // (r4f_short_mma, r4f_dense_wide_bf16; the bf16 image keeps the K-split tiles).  fp32: N-split, K split over the lane quarters
+    // of every wave (r4f_short_mma_ns, r4f_dense_wide_ns; barriers and hazards: make_r4_lds).  The two never mix: the ReLU sign
+    // words are per thread, and writer and reader must agree on the lane-to-output mapping.
+    const int kq = FAST ? t.wave : t.lane >> 4;            // whose quarter of K = 32 this lane multiplies in S1 / S4
     R4FRing<NTWM, FAST, NS> ring(reinterpret_cast<const float4*>(packed + (FAST ? f.o_r4fh : f.o_r4f)), t, stash);
     const char* pf_img = reinterpret_cast<const char*>(packed + (FAST ? f.o_r4fh : f.o_r4f));
     const float* pf_junk = lds + l.o_PF + 64 * t.wave;             // (r4f_prefetch_l2)
@@ -540,20 +614,25 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
         unsigned* mk = reinterpret_cast<unsigned*>(lds + l.o_MASK) + (size_t)layer * 2 * NTHREADS;
         const bool tl = layer == f.K - 2;
         if (tl) FAB_TL(f, 0);
-        {   // S1: h1 = relu(y W1' + b1'), z = y A + ac   (K = 32: k in [8 w, 8 w + 8) on this wave)
-            const float* xr = X + t.arow * R4_DS + 8 * t.wave;
+        {   // S1: h1 = relu(y W1' + b1'), z = y A + ac   (K = 32: k in [8 kq, 8 kq + 8), kq = this wave (FAST) / this lane quarter)
+            const float* xr = X + t.arow * R4_DS + 8 * kq;
             const float4 a0 = *reinterpret_cast<const float4*>(xr), a1 = *reinterpret_cast<const float4*>(xr + 4);
+            // the z path stays K-split over the waves (dense tile: k-quad 2 w + sblk)
+            float4 az;
+            if constexpr (FAST) az = sblk ? a1 : a0;
+            else az = *reinterpret_cast<const float4*>(X + t.arow * R4_DS + 8 * t.wave + 4 * sblk);
+            f32x4 acc[G];                                  // (N-split: lane quarter Q's partial of this wave's own columns)
 #ifdef FAB_R4F_WAVETL                  // dev-only (tools/experiments/dephase): per-wave stamps around the refills of S1
             long long wt[8];
 #define FAB_WT(k) do { __builtin_amdgcn_sched_barrier(0); wt[k] = (long long)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
             FAB_WT(0);
             {
-                f32x4 acc0[G], acc1[G];
+                f32x4 acc1[G];
 #pragma unroll
-                for (int g = 0; g < G; ++g) { acc0[g] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1[g] = acc0[g]; }
+                for (int g = 0; g < G; ++g) { acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1[g] = acc[g]; }
                 ring.wait(IC<0>{});
                 FAB_WT(1);
-                r4_quad<G>(a0, ring.r[ring.slot(IC<0>{})], acc0);
+                r4_quad<G>(a0, ring.r[ring.slot(IC<0>{})], acc);
                 FAB_WT(2);
                 ring.refill(IC<0>{});
                 FAB_WT(3);
@@ -563,24 +642,31 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
                 ring.refill(IC<1>{});
                 FAB_WT(5);
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc0[g] += acc1[g];
-                r4_store_part_rf<G>(acc0, PART, t);
+                for (int g = 0; g < G; ++g) acc[g] += acc1[g];
+                if constexpr (FAST) r4_store_part_rf<G>(acc, PART, t);
             }
 #else
-            r4f_short_mma<NTWM, 0>(a0, a1, ring, PART, l.PN, t);
+            if constexpr (FAST) r4f_short_mma<NTWM, 0>(a0, a1, ring, PART, l.PN, t);
+            else r4f_short_mma_ns<NTWM, 0>(a0, a1, ring, acc);
 #endif
             R4FAcc z;
             ring.wait(IC<S::I_A>{});
-            z.template tile<0>(sblk ? a1 : a0, ring.r[ring.slot(IC<S::I_A>{})][0]);
+            z.template tile<0>(az, ring.r[ring.slot(IC<S::I_A>{})][0]);
             ring.refill(IC<S::I_A>{});
             r4f_prefetch_l2<S::TL>(pf_junk, pf_voff, pf_img, pf_slot++, 2 * f.K);
 #ifdef FAB_R4F_WAVETL
             FAB_WT(6);
 #endif
-            z.store(PZ, t);
+            // N-split: the z partials go to PART, which no stage of this direction writes before S3's barriers (in PZ they would
+            // race with S3's p.store from a wave that runs ahead through the barrier-free S2)
+            z.store(FAST ? PZ : PART, t);
             float bv[G];
-            r4_bias_rf<G>(bv, bt, t);
-            r4_barrier();
+            if constexpr (FAST) r4_bias_rf<G>(bv, bt, t);
+            else {
+                r4_bias_ns<G>(bv, bt, t);
+                r4_epilogue_ns<G, 1>(acc, bv, HA, l.WS, mk, t);
+            }
+            r4_barrier();              // (FAST: partials visible; N-split: the stage's END - S2 reads all of HA)
 #ifdef FAB_R4F_WAVETL
             FAB_WT(7);
             if (tl && f.timeline && blockIdx.x == 0 && t.lane == 0) {
@@ -588,16 +674,21 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
                 for (int k = 0; k < 8; ++k) f.timeline[32 + 8 * t.wave + k] = wt[k];
             }
 #endif
-            float zv = 0.f;                                // (read before the wide epilogue's writes: one LDS round trip less)
-            if (t.tid < 128) zv = r4f_tree8(PZ, zrow, zc) + bt[2 * f.Wp + zc];
-            r4_epilogue_rf<G, 1>(PART, bv, HA, l.WS, mk, t);
-            if (t.tid < 128) X[zrow * R4_DS + zc] = zv;    // (read next in S3: S2's barrier makes it visible)
-            r4_wave_handover();
+            if constexpr (FAST) {
+                float zv = 0.f;                            // (read before the wide epilogue's writes: one LDS round trip less)
+                if (t.tid < 128) zv = r4f_tree8(PZ, zrow, zc) + bt[2 * f.Wp + zc];
+                r4_epilogue_rf<G, 1>(PART, bv, HA, l.WS, mk, t);
+                if (t.tid < 128) X[zrow * R4_DS + zc] = zv;    // (read next in S3: S2's barrier makes it visible)
+                r4_wave_handover();
+            } else if (t.tid < 128) {
+                // (every wave's reads of X are in front of the barrier above; read next in S3's epilogue, behind S3's first barrier)
+                X[zrow * R4_DS + zc] = r4f_tree8(PART, zrow, zc) + bt[2 * f.Wp + zc];
+            }
         }
         logq += bt[2 * f.Wp + 64];
         if (tl) FAB_TL(f, 1);
         if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART2, t);
-        else r4f_dense_wide<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, PART2, l.PN, t);
+        else r4f_dense_wide_ns<NTWM, 1>(HA, l.WS, ring, bt + f.Wp, HB, l.WS, mk + NTHREADS, t);
         if (tl) FAB_TL(f, 3);
         {   // S3: (shift | s) = h2 W3 + b3, then AffineCoupling.inverse: z2 <- (z2 - shift) exp(-s), log_det = -sum(s)
             R4FAcc p;
@@ -654,9 +745,11 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
         if (tl) FAB_TL(f, 16);
         f32x4 atile;
         {   // S4: (shift | scale) cotangents -> hidden (K = 32)
-            const float* dr = DP + t.arow * R4_DS + 8 * t.wave;
+            const float* dr = DP + t.arow * R4_DS + 8 * kq;
             const float4 a0 = *reinterpret_cast<const float4*>(dr), a1 = *reinterpret_cast<const float4*>(dr + 4);
-            r4f_short_mma<NTWM, 0>(a0, a1, ring, PART, l.PN, t);
+            f32x4 acc[G];                                  // (N-split: lane quarter Q's partial of this wave's own columns)
+            if constexpr (FAST) r4f_short_mma<NTWM, 0>(a0, a1, ring, PART, l.PN, t);
+            else r4f_short_mma_ns<NTWM, 0>(a0, a1, ring, acc);
             ring.wait(IC<S::I_A>{});
             {   // A^T: used by S6.  Copied out of the ring into VGPRs - an opaque copy: if `atile` merely aliased the slot's register,
                 // the slot's next request would get ANOTHER register and hipcc would copy that in-flight register back at the
@@ -671,13 +764,18 @@ __device__ float flow_log_prob_r4f(const FlowDims& f, const R4Lds& l, const floa
             float bv[G];
 #pragma unroll
             for (int g = 0; g < G; ++g) bv[g] = 0.f;
-            r4_barrier();
-            r4_epilogue_rf<G, 2>(PART, bv, HA, l.WS, mk + NTHREADS, t);
-            r4_wave_handover();
+            if constexpr (FAST) {
+                r4_barrier();
+                r4_epilogue_rf<G, 2>(PART, bv, HA, l.WS, mk + NTHREADS, t);
+                r4_wave_handover();
+            } else {
+                r4_epilogue_ns<G, 2>(acc, bv, HA, l.WS, mk + NTHREADS, t);
+                r4_barrier();          // (the stage's END: S5 reads all of HA)
+            }
         }
         if (tl) FAB_TL(f, 18);
         if constexpr (FAST) r4f_dense_wide_bf16<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART2, t);
-        else r4f_dense_wide<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, PART2, l.PN, t);
+        else r4f_dense_wide_ns<NTWM, 2>(HA, l.WS, ring, nullptr, HB, l.WS, mk, t);
         if (tl) FAB_TL(f, 19);
         {   // S6: g_y = dh1 W1'^T + g_z A^T, then the coupling cotangents of layer + 1
             R4FAcc p;
