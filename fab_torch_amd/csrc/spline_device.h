@@ -395,7 +395,11 @@ __device__ __forceinline__ void rqs_inverse(const Rqs& s, float y, float tb, flo
     const float bq = h * d0 - dy * A;
     const float c = -dl * dy;
     const float disc = bq * bq - 4.f * a * c;
-    const float root = (2.f * c) * sp_rcp(-bq - sqrtf(disc));
+    // (on a knot whose derivative is near SP_MIN_D the discriminant is (h d)^2, the difference of two terms ~ (2 h dl)^2: it rounds
+    // below zero there - the sample was NaN - and the bin fraction leaves [0, 1] by up to d / (2 dl), enough to turn `dn` below
+    // negative - log q was NaN beside a finite x).  fmaxf / fminf return the other operand for a NaN: a NaN root (NaN parameters)
+    // becomes 0 here, and the NaN still reaches x and ld through w, xk and dl
+    const float root = fminf(fmaxf((2.f * c) * sp_rcp(-bq - sqrtf(fmaxf(disc, 0.f))), 0.f), 1.f);
     x = root * w + xk;
     const float t1 = root * (1.f - root);
     const float den = dl + A * t1;
