@@ -7,7 +7,7 @@ that is impossible — there is no CPU fallback."""
 from .point import Point
 from .flow import RealNVP, make_wrapped_normflow_realnvp
 from .defensive import DefensiveMixtureDistribution
-from .targets import ManyWellEnergy, GMM, CoupledQuarticEnergy, LatticePhi4
+from .targets import ManyWellEnergy, GMM, CoupledQuarticEnergy, LatticePhi4, CoupledRotorEnergy, LatticeXY
 from .transition_operators import (TransitionOperator, HamiltonianMonteCarlo, Metropolis, create_point, grad_and_value,
                                    get_intermediate_log_prob, get_grad_intermediate_log_prob)
 from .ais import AnnealedImportanceSampler, LoggingInfo, NoValidPoints
@@ -41,7 +41,8 @@ class fast_mode:
 
 
 __all__ = [
-    "Point", "RealNVP", "make_wrapped_normflow_realnvp", "ManyWellEnergy", "GMM", "CoupledQuarticEnergy", "LatticePhi4", "TransitionOperator",
+    "Point", "RealNVP", "make_wrapped_normflow_realnvp", "ManyWellEnergy", "GMM", "CoupledQuarticEnergy", "LatticePhi4", "CoupledRotorEnergy", "LatticeXY",
+    "TransitionOperator",
     "HamiltonianMonteCarlo", "Metropolis", "create_point", "grad_and_value", "get_intermediate_log_prob",
     "get_grad_intermediate_log_prob", "AnnealedImportanceSampler", "LoggingInfo", "NoValidPoints",
     "effective_sample_size", "ess_and_log_z", "resample", "multinomial_indices", "systematic_indices",

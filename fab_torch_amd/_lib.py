@@ -78,7 +78,7 @@ class AisArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC = 1, 2, 3
+TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC, TARGET_ROTOR = 1, 2, 3, 4
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
 
 _lib = None
@@ -140,7 +140,7 @@ SYMBOLS = [
     "fabhip_next_beta", "fabhip_log_w_first",
     "fabhip_flow_move_workspace_bytes", "fabhip_flow_move",
 ]
-ABI_VERSION = 226          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
+ABI_VERSION = 227          # FABHIP_ABI_VERSION of include/fabhip.h this binding was written against
 
 
 def _declare(lib):

@@ -14,9 +14,9 @@ import torch
 
 from . import _build
 
-ABI_VERSION = 226          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
+ABI_VERSION = 227          # FABHIP_ABI_VERSION of include/fabhip.h the Python side was written against
 
-TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC = 1, 2, 3
+TARGET_MANYWELL, TARGET_GMM, TARGET_QUARTIC, TARGET_ROTOR = 1, 2, 3, 4
 TRANSITION_HMC, TRANSITION_METROPOLIS = 1, 2
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_FAST = 0, 1, 2          # FABHIP_PRECISION_* (per-call fast mode)
 

@@ -117,7 +117,7 @@ void fill_params(fabhip_flow_params& p, at::TensorList params, int64_t dim, int6
         }
 }
 
-// `ref`: the tensor whose device the launch is enqueued for (the quartic target's tensors must live there).
+// `ref`: the tensor whose device the launch is enqueued for (the quartic and the rotor target's tensors must live there).
 fabhip_target make_target(int64_t kind, at::ArrayRef<double> prm, const optional<Tensor>& locs,
                           const optional<Tensor>& scales, int64_t dim, const Tensor& ref) {
     TORCH_CHECK(prm.size() == 4, "fabhip: target parameters are {a, b, c, log_norm}");
@@ -140,6 +140,20 @@ fabhip_target make_target(int64_t kind, at::ArrayRef<double> prm, const optional
         TORCH_CHECK(scales->dim() == 2 && scales->size(0) == 3 && scales->size(1) == dim, "fabhip: quartic site coefficients "
                     "must be [3, ", dim, "], got ", scales->sizes());
         t.locs = fpn(*locs, dim * dim, ref, "quartic coupling"); t.scales = fpn(*scales, 3 * dim, ref, "quartic site coefficients");
+    }
+    if (kind == FABHIP_TARGET_ROTOR) {        // locs = neighbour table [2 NB, D] (indices, then couplings), scales = site rows [9, D]
+        TORCH_CHECK(locs.has_value() && scales.has_value(), "fabhip: rotor target needs the neighbour table (locs) and the site "
+                    "rows (scales)");
+        TORCH_CHECK(dim >= 1 && dim <= FABHIP_MAX_DIM, "fabhip: rotor target needs 1 <= dim <= ", FABHIP_MAX_DIM, ", got ", dim);
+        TORCH_CHECK(scales->dim() == 2 && scales->size(0) == 9 && scales->size(1) == dim, "fabhip: rotor site rows must be [9, ",
+                    dim, "], got ", scales->sizes());
+        TORCH_CHECK(locs->dim() == 2 && locs->size(1) == dim && locs->size(0) % 2 == 0, "fabhip: rotor neighbour table must be "
+                    "[2 NB, ", dim, "], got ", locs->sizes());
+        const int64_t nb = locs->size(0) / 2;
+        TORCH_CHECK(nb >= 1 && nb <= FABHIP_MAX_DIM - 1, "fabhip: rotor neighbour table needs 1 <= NB <= ", FABHIP_MAX_DIM - 1,
+                    ", got ", nb);
+        t.n_mix = (int32_t)nb;
+        t.locs = fpn(*locs, 2 * nb * dim, ref, "rotor neighbour table"); t.scales = fpn(*scales, 9 * dim, ref, "rotor site rows");
     }
     return t;
 }

@@ -1,7 +1,8 @@
 """Target distributions of the hot path: ManyWell (fab/target_distributions/many_well.py:16-90,
 double_well.py:31-58) and the 40-mode GMM (fab/target_distributions/gmm.py:12-66) — same constructor
 arguments and `log_prob` semantics; `log_prob` runs csrc/target_device.h on the GPU.  `CoupledQuarticEnergy` / `LatticePhi4`: the
-coupled-quartic family (no counterpart in the reference; tests/quartic_cases.py is its definition)."""
+coupled-quartic family (no counterpart in the reference; tests/quartic_cases.py is its definition).  `CoupledRotorEnergy` / `LatticeXY`:
+the periodic family, coupled rotors (tests/rotor_cases.py is its definition)."""
 import math
 
 import numpy as np
@@ -422,3 +423,224 @@ class LatticePhi4(CoupledQuarticEnergy):
         w = torch.softmax(log_w.double(), 0)
         return {"abs_magnetisation": float((w * m.abs()).sum()), "magnetisation_sq": float((w * m * m).sum()),
                 "positive_share": float((w * (m > 0).double()).sum())}
+
+
+class CoupledRotorEnergy(_NativeTarget):
+    """Coupled rotors: periodic sites with Fourier terms and couplings in angle differences, next to harmonic sites on the line,
+        t_j = x_j r_j,  w_j = t_j - rint(t_j),  theta_j = 2 pi w_j,  d_jk = (w_j - w_k) - rint(w_j - w_k),
+        log p(x) = sum_j [sum_{m=1..3} (A_mj cos m theta_j + B_mj sin m theta_j) - l_j x_j - q_j x_j^2]
+                   + 1/2 sum_j sum_k K_jk cos(2 pi d_jk) - log_norm,                                          D <= 64,
+    r_j = 1 / period_j (period_j = 0: a site on the line, r_j = 0).  The fourth branch of csrc/target_device.h evaluates it on
+    every route of the fused path: lattice XY (`LatticeXY`), torsion angles with Fourier terms and harmonic bonds, a torus shared
+    with `CircularCoupledRQSFlow` (`for_flow`).  The definition is tests/rotor_cases.py.  The kernels read the coupling as a
+    neighbour table that lists every bond from both ends; this class builds it from the symmetric matrix, so the contract is
+    kept here.  Checks run in float64 on the host; the device holds float32 copies."""
+
+    MAX_DIM = 64                                                    # FABHIP_MAX_DIM
+    N_HARMONICS = 3
+
+    def __init__(self, period, fourier_cos, fourier_sin, coupling, line_linear=None, line_quadratic=None,
+                 normalised: bool = False, use_gpu: bool = True):
+        super().__init__()
+        name = type(self).__name__
+        h = lambda v: torch.as_tensor(v).detach().to("cpu", torch.float64)             # noqa: E731
+        P = h(period)
+        if P.dim() != 1 or P.shape[0] < 1:
+            raise ValueError(f"{name}: period must be [D] with D >= 1, got {tuple(P.shape)}")
+        D = int(P.shape[0])
+        if D > self.MAX_DIM:
+            raise ValueError(f"{name}: dim = {D} is above the {self.MAX_DIM} sites the kernels hold")
+        A, B, K = h(fourier_cos), h(fourier_sin), h(coupling)
+        l = torch.zeros(D, dtype=torch.float64) if line_linear is None else h(line_linear)
+        q = torch.zeros(D, dtype=torch.float64) if line_quadratic is None else h(line_quadratic)
+        A, B = (v[None] if v.dim() == 1 else v for v in (A, B))                        # [D]: the first harmonic alone
+        if A.dim() != 2 or A.shape[1] != D or not 1 <= A.shape[0] <= self.N_HARMONICS or B.shape != A.shape \
+                or tuple(K.shape) != (D, D) or l.shape != (D,) or q.shape != (D,):
+            raise ValueError(f"{name}: fourier_cos and fourier_sin must be [D] or [m, D] with m <= {self.N_HARMONICS}, coupling "
+                             f"[D, D], line_linear and line_quadratic [D] for D = {D}, got {tuple(A.shape)}, {tuple(B.shape)}, "
+                             f"{tuple(K.shape)}, {tuple(l.shape)} and {tuple(q.shape)}")
+        pad = torch.zeros(self.N_HARMONICS - A.shape[0], D, dtype=torch.float64)
+        A, B = torch.cat([A, pad]), torch.cat([B, pad])
+        if not all(bool(torch.isfinite(v).all()) for v in (P, A, B, K, l, q)):
+            raise ValueError(f"{name}: a period, a coefficient or a coupling is not finite")
+        if bool((P < 0).any()):
+            raise ValueError(f"{name}: a period is negative (0 marks a site on the line)")
+        if float((K - K.T).abs().max()) > 1e-6 * float(K.abs().max()):
+            raise ValueError(f"{name}: the coupling is not symmetric (every bond is listed from both ends)")
+        K = 0.5 * (K + K.T)
+        if bool((torch.diagonal(K) != 0).any()):
+            raise ValueError(f"{name}: the coupling has a non-zero diagonal (a site's bond to itself is a constant)")
+        line = P == 0
+        if bool((K[line] != 0).any()):
+            raise ValueError(f"{name}: the coupling touches a site on the line (it acts on angle differences)")
+        if bool(((l != 0) | (q != 0))[~line].any()):
+            raise ValueError(f"{name}: line_linear / line_quadratic are set on a periodic site (the density would not be periodic)")
+        if bool(((A != 0) | (B != 0)).any(0)[line].any()):
+            raise ValueError(f"{name}: Fourier coefficients are set on a site on the line (it has no angle)")
+        if bool((q[line] <= 0).any()):
+            raise ValueError(f"{name}: line_quadratic must be > 0 on a site on the line (the density could not be normalised)")
+        self.dim, self.normalised = D, bool(normalised)
+        rate = torch.where(line, torch.zeros_like(P), 1.0 / torch.where(line, torch.ones_like(P), P))
+        self._P64, self._A64, self._B64, self._K64, self._l64, self._q64, self._line = P, A, B, K, l, q, line
+        idx, kap = self.neighbour_table(K)
+        self.n_neighbours = int(idx.shape[0])
+        self.register_buffer("table", torch.cat([idx, kap]).float().contiguous())                  # fabhip_target.locs   [2 NB][D]
+        self.register_buffer("site_rows", torch.cat([A, B, rate[None], l[None], q[None]]).float().contiguous())    # .scales [9][D]
+        self.register_buffer("period", P.float())
+        self._log_Z = None
+        if self.normalised:
+            self.log_Z                                                # raises where no exact constant exists
+        self.device = "cuda" if (use_gpu and torch.cuda.is_available()) else "cpu"
+        if self.device == "cuda":
+            self.cuda()
+
+    @staticmethod
+    def neighbour_table(K):
+        """(indices [NB, D], couplings [NB, D]) in float64: column j lists the k with K[j, k] != 0 in ascending k and pads with
+        k = j, kap = 0; NB = max(1, largest count)."""
+        D = K.shape[0]
+        rows = [torch.nonzero(K[j] != 0).flatten() for j in range(D)]
+        NB = max(1, max(int(r.numel()) for r in rows))
+        idx = torch.arange(D, dtype=torch.float64)[None].repeat(NB, 1)
+        kap = torch.zeros(NB, D, dtype=torch.float64)
+        for j, r in enumerate(rows):
+            idx[:r.numel(), j] = r.double()
+            kap[:r.numel(), j] = K[j, r]
+        return idx, kap
+
+    @classmethod
+    def for_flow(cls, spline_flow, fourier_cos, fourier_sin, coupling, line_linear=None, line_quadratic=None, **kw):
+        """The target on the torus of `spline_flow` (a CircularCoupledRQSFlow): period_j = 2 tail_bound_j on the flow's circular
+        coordinates, 0 elsewhere."""
+        circ, tb = spline_flow._circ.cpu(), spline_flow._tail_bound.detach().cpu().double()
+        return cls(torch.where(circ, 2.0 * tb, torch.zeros_like(tb)), fourier_cos, fourier_sin, coupling, line_linear,
+                   line_quadratic, **kw)
+
+    # ---- the exact cases ------------------------------------------------------------------------------------------------------
+    @property
+    def is_independent(self) -> bool:
+        return bool((self._K64 == 0).all())
+
+    @property
+    def is_single_harmonic(self) -> bool:
+        return bool((self._A64[1:] == 0).all() and (self._B64[1:] == 0).all())
+
+    def _site_log_z(self, j):
+        """log of the integral of site j's factor over one period (periodic) or over the line, float64"""
+        if bool(self._line[j]):
+            l, q = float(self._l64[j]), float(self._q64[j])
+            return 0.5 * math.log(math.pi / q) + l * l / (4.0 * q)
+        P, A, B = float(self._P64[j]), self._A64[:, j], self._B64[:, j]
+        if bool((A[1:] == 0).all() and (B[1:] == 0).all()):
+            kappa = torch.sqrt(A[0] * A[0] + B[0] * B[0])
+            return math.log(P) + float(torch.log(torch.special.i0e(kappa)) + kappa)
+        n = 4096                                                     # periodic and analytic: the trapezoid rule converges spectrally
+        th = 2.0 * math.pi * torch.arange(n, dtype=torch.float64) / n
+        m = torch.arange(1, self.N_HARMONICS + 1, dtype=torch.float64)[:, None]
+        e = (A[:, None] * torch.cos(m * th) + B[:, None] * torch.sin(m * th)).sum(0)
+        return float(torch.logsumexp(e, 0)) + math.log(P / n)
+
+    @property
+    def log_Z(self) -> torch.Tensor:
+        """float64, over one period of every periodic site and the line of every other; known without a coupling only."""
+        if self._log_Z is None:
+            if not self.is_independent:
+                raise NotImplementedError(f"{type(self).__name__}: log_Z is known without a coupling only")
+            self._log_Z = torch.as_tensor(sum(self._site_log_z(j) for j in range(self.dim)), dtype=torch.float64)
+        return self._log_Z
+
+    @property
+    def Z(self):
+        return torch.exp(self.log_Z)
+
+    def native_target(self):
+        log_norm = float(self.log_Z) if self.normalised else 0.0
+        return _ops.TARGET_ROTOR, [0.0, 0.0, 0.0, log_norm], self.table, self.site_rows
+
+    def log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        return _target_log_prob(self, x)
+
+    def energy(self, x, temperature=None):
+        assert x.shape[-1] == self.dim, "`x` does not match `dim`"
+        return -self.log_prob(x)[..., None] / (1.0 if temperature is None else temperature)
+
+    def force(self, x, temperature=None):
+        assert x.shape[-1] == self.dim, "`x` does not match `dim`"
+        _, g = self.log_prob_and_grad(x.detach().contiguous().float())
+        return g / (1.0 if temperature is None else temperature)
+
+    def wrap(self, x: torch.Tensor) -> torch.Tensor:
+        """Periodic coordinates mapped to [-P/2, P/2); coordinates on the line and coordinates already inside are returned as
+        they are (so that wrap is idempotent)."""
+        P = self.period.to(x.device, x.dtype)
+        safe = torch.where(P > 0, P, torch.ones_like(P))
+        y = x - safe * torch.floor(x / safe + 0.5)
+        y = torch.where(y >= 0.5 * safe, y - safe, torch.where(y < -0.5 * safe, y + safe, y))
+        inside = (x >= -0.5 * safe) & (x < 0.5 * safe)
+        return torch.where((P > 0) & ~inside, y, x)
+
+    def sample(self, shape) -> torch.Tensor:
+        """Exact samples without a coupling and with single-harmonic sites: von Mises angles (drawn on the host) and Gaussians."""
+        if not (self.is_independent and self.is_single_harmonic):
+            raise NotImplementedError(f"{type(self).__name__}: exact samples exist without a coupling and for single-harmonic "
+                                      "sites only")
+        assert len(shape) == 1
+        n = int(shape[0])
+        A, B, P, line = self._A64[0], self._B64[0], self._P64, self._line
+        kappa, phi = torch.sqrt(A * A + B * B), torch.atan2(B, A)
+        x = torch.empty(n, self.dim, dtype=torch.float64)
+        for j in range(self.dim):
+            if bool(line[j]):
+                l, q = float(self._l64[j]), float(self._q64[j])
+                x[:, j] = -l / (2.0 * q) + torch.randn(n, dtype=torch.float64) / math.sqrt(2.0 * q)
+            elif float(kappa[j]) < 1e-12:
+                x[:, j] = (torch.rand(n, dtype=torch.float64) - 0.5) * P[j]
+            else:
+                th = torch.distributions.VonMises(phi[j], kappa[j]).sample((n,))
+                x[:, j] = th * P[j] / (2.0 * math.pi)
+        return x.float().to(self.table.device)
+
+
+class LatticeXY(CoupledRotorEnergy):
+    """The XY model on a periodic lattice of prod(shape) <= 64 sites, any number of dimensions:
+        log p = coupling sum over bonds cos(theta_x - theta_y) + field sum_x cos(theta_x),   theta_x = 2 pi x / period.
+    The bonds are those the sum over (x, mu) meets: an extent of 2 joins two sites twice (K = 2 coupling between them), an extent
+    of 1 joins a site to itself - a constant, left out of the table."""
+
+    def __init__(self, shape, coupling: float, field: float = 0.0, period: float = 2.0 * math.pi, normalised: bool = False,
+                 use_gpu: bool = True):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) < 1 or any(s < 1 for s in shape):
+            raise ValueError(f"LatticeXY: shape must hold positive extents, got {shape}")
+        D = int(np.prod(shape))
+        if D > self.MAX_DIM:
+            raise ValueError(f"LatticeXY: {shape} has {D} sites, above the {self.MAX_DIM} the kernels hold")
+        idx = np.arange(D).reshape(shape)
+        K = torch.zeros(D, D, dtype=torch.float64)
+        n_bonds = 0
+        for mu in range(len(shape)):
+            if shape[mu] == 1:
+                continue
+            x, y = torch.as_tensor(idx.reshape(-1)), torch.as_tensor(np.roll(idx, -1, axis=mu).reshape(-1))
+            K.index_put_((x, y), torch.full((D,), float(coupling), dtype=torch.float64), accumulate=True)
+            K.index_put_((y, x), torch.full((D,), float(coupling), dtype=torch.float64), accumulate=True)
+            n_bonds += D
+        super().__init__(torch.full((D,), float(period), dtype=torch.float64), torch.full((D,), float(field), dtype=torch.float64),
+                         torch.zeros(D, dtype=torch.float64), K, normalised=normalised, use_gpu=use_gpu)
+        self.shape, self.coupling_strength, self.field, self.n_bonds = shape, float(coupling), float(field), n_bonds
+
+    def performance_metrics(self, samples, log_w, log_q_fn=None, batch_size=None):
+        """Importance-weighted |mean_x exp(i theta_x)| (the magnetisation per site), its square, and the mean cosine over the
+        nearest-neighbour bonds (1 for an ordered lattice, 0 without bonds or without order)."""
+        del log_q_fn, batch_size
+        th = samples.double().cpu() * (2.0 * math.pi / float(self._P64[0]))
+        w = torch.softmax(log_w.double().cpu(), 0)
+        m2 = torch.cos(th).mean(-1) ** 2 + torch.sin(th).mean(-1) ** 2
+        f = th.reshape((th.shape[0],) + self.shape)
+        nn_cos = torch.zeros(th.shape[0], dtype=torch.float64)
+        for mu in range(len(self.shape)):
+            if self.shape[mu] > 1:
+                nn_cos += torch.cos(f - torch.roll(f, -1, dims=mu + 1)).reshape(th.shape[0], -1).sum(-1)
+        nn_cos = nn_cos / max(self.n_bonds, 1)
+        return {"abs_magnetisation": float((w * m2.sqrt()).sum()), "magnetisation_sq": float((w * m2).sum()),
+                "neighbour_cosine": float((w * nn_cos).sum())}

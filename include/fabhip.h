@@ -37,7 +37,7 @@ const char* fabhip_strerror(int code);
 /* ABI revision of this header: bumped on every change of a struct layout or a function signature.  The host
  * binding compares it (and the struct sizes below) with what it was written against and refuses to run on a
  * mismatch, so that a stale library can never be driven with newer struct layouts. */
-#define FABHIP_ABI_VERSION 226
+#define FABHIP_ABI_VERSION 227
 int fabhip_version(void);
 /* sizeof() of the argument structs as the library was compiled:
  * {fabhip_flow_params, fabhip_flow, fabhip_target, fabhip_point, fabhip_anneal, fabhip_hmc_args,
@@ -368,16 +368,27 @@ int fabhip_train_step_plan(int32_t dim, int32_t n_layers, int32_t width, int64_t
 /* FABHIP_TARGET_QUARTIC (ABI 224): coupled quartic sites (lattice phi^4, coupled double wells, correlated Gaussians),
  *   log p(x) = - sum_j (a_j x_j + b_j x_j^2 + c_j x_j^4) - 1/2 sum_j x_j (J x)_j - log_norm,   1 <= dim <= FABHIP_MAX_DIM,
  * with J SYMMETRIC (the kernels read J[k][j] for (J x)_j and do not check it).  NaN / inf coordinates propagate. */
-enum { FABHIP_TARGET_MANYWELL = 1, FABHIP_TARGET_GMM = 2, FABHIP_TARGET_QUARTIC = 3 };
+/* FABHIP_TARGET_ROTOR (ABI 227): coupled rotors (lattice XY, torsion angles with Fourier terms, harmonic line sites),
+ *   t_j = x_j r_j,  w_j = t_j - rint(t_j),  theta_j = 2 pi w_j,  d_jn = (w_j - w_k) - rint(w_j - w_k) with k = k_jn,
+ *   log p(x) = sum_j [sum_{m=1..3} (A_mj cos m theta_j + B_mj sin m theta_j) - l_j x_j - q_j x_j^2]
+ *              + 1/2 sum_j sum_{n<NB} kap_jn cos(2 pi d_jn) - log_norm,                         1 <= dim <= FABHIP_MAX_DIM.
+ * r_j = 1 / period of a periodic site, 0 of a site on the line.  The neighbour table is the row form of a SYMMETRIC coupling
+ * with a zero diagonal: every bond listed from both ends (the gradient relies on it and the kernels do not check it), unused
+ * slots padded with k = j, kap = 0.  Every index entry must be a FINITE float (the kernels convert it to an integer; a NaN or inf
+ * entry has no defined conversion); a finite index outside 0 .. dim - 1 is clamped.  NaN / inf coordinates propagate. */
+enum { FABHIP_TARGET_MANYWELL = 1, FABHIP_TARGET_GMM = 2, FABHIP_TARGET_QUARTIC = 3, FABHIP_TARGET_ROTOR = 4 };
 
 typedef struct {
     int32_t kind, dim;
     float a, b, c;       /* many well: energy a x + b x^2 + c x^4 on even dims, x^2/2 on odd     */
-    float log_norm;      /* subtracted from log p (0 unless `normalised`); many well and quartic */
-    int32_t n_mix;       /* GMM: number of equally weighted components; unused otherwise         */
-    const float* locs;   /* GMM: [n_mix][dim]; quartic: the coupling J, [dim][dim], symmetric    */
-    const float* scales; /* GMM: [n_mix][dim] diagonal of scale_tril; quartic: the site          */
-                         /* coefficients [3][dim], rows a, b, c                                  */
+    float log_norm;      /* subtracted from log p (0 unless `normalised`); many well, quartic and rotor */
+    int32_t n_mix;       /* GMM: number of equally weighted components; rotor: the neighbour table's     */
+                         /* width NB, 1 .. 63; unused otherwise                                          */
+    const float* locs;   /* GMM: [n_mix][dim]; quartic: the coupling J, [dim][dim], symmetric; rotor:    */
+                         /* [2 NB][dim], rows 0 .. NB - 1 the neighbour indices as floats, rows NB ..    */
+                         /* 2 NB - 1 the couplings                                                       */
+    const float* scales; /* GMM: [n_mix][dim] diagonal of scale_tril; quartic: the site coefficients     */
+                         /* [3][dim], rows a, b, c; rotor: [9][dim], rows A1 A2 A3 B1 B2 B3 r l q        */
 } fabhip_target;
 
 int fabhip_target_log_prob(const fabhip_target* target, const float* x, float* log_p, float* grad_x,

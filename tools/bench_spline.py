@@ -1,6 +1,8 @@
 """BASELINE cfg 3 with the flow family it names: ManyWell-32, spline flow 12 layers (hidden 256, 8 bins), 2048 chains,
 12 intermediate distributions, HMC(5 leapfrogs) - through the generic plug-in path (spline kernels + elementwise
-transition kernels).  Prints AIS samples/s and the time of one log_prob_and_grad / sample call."""
+transition kernels).  Prints AIS samples/s and the time of one log_prob_and_grad / sample call.  CFG=5: the 60-D shape of
+BASELINE cfg 5; TARGET=rotor: the coupled-rotor stand-in of tools/bench_targets.py (periodic on the flow's circular coordinates)
+in place of ManyWell."""
 import json, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,6 +24,9 @@ with torch.no_grad():
         if p.dim() == 2 and p.shape[0] % 25 == 0:
             p.add_(0.02 * torch.randn_like(p))
 target = fa.ManyWellEnergy(D)
+if os.environ.get("TARGET") == "rotor":                # the coupled-rotor stand-in on the flow's own torus (CFG=5: 12 coupled torsions)
+    from bench_targets import torsion_stand_in
+    target = torsion_stand_in(flow)
 hmc = fa.HamiltonianMonteCarlo(M, D, flow.log_prob, target.log_prob, alpha=2.0, p_target=False, epsilon=0.1, L=LF).to(DEV)
 ais = fa.AnnealedImportanceSampler(flow, target.log_prob, hmc, False, 2.0, M)
 
@@ -38,7 +43,7 @@ def timeit(fn, n, warm=3):
 
 
 x, _ = flow.sample_and_log_prob((B,))
-out = {"config": f"ManyWell-{D}, spline {L}x(hidden {H}, 8 bins, {len(CIRC)} circular), {B} chains, M={M}, HMC L={LF}"}
+out = {"config": f"{'rotor stand-in' if os.environ.get('TARGET') == 'rotor' else 'ManyWell'}-{D}, spline {L}x(hidden {H}, 8 bins, {len(CIRC)} circular), {B} chains, M={M}, HMC L={LF}"}
 out["log_prob_and_grad_ms"] = 1e3 * timeit(lambda: flow.log_prob_and_grad(x), 50)
 out["log_prob_ms"] = 1e3 * timeit(lambda: flow.log_prob(x), 50)
 out["sample_ms"] = 1e3 * timeit(lambda: flow.sample_and_log_prob((B,)), 50)
