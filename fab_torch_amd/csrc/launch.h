@@ -80,6 +80,9 @@ int spline_log_prob_leap(const fabhip_spline_flow* flow, const SplineLeap& lp, f
 // The tail of a chain phase in one launch for small batches (reduce_kernels.hip: k_tail_small): compaction of the rows with
 // finite log_p / log_q, optionally diff = log_p - log_q over all B rows, ESS / log Z over the survivors (of diff, or of log_w).
 // FABHIP_ENOTSUP above 2048 rows (the caller then runs the separate kernels: the same results, bit for bit).
+// Both forms write the first n_out rows only: rows in [n_out, n_in) keep what they held (this kernel writes a row only at its
+// destination < n_out, k_compact_copyback copies rows < n_out back), rows at and beyond n_in are never touched - so the two
+// forms leave the WHOLE arrays bit-equal (tests/test_gpu_tail.py compares them so).
 struct TailArgs {
     float *x, *lq, *lp, *gq, *gp;      // the point's fields (gq / gp null: a Metropolis run)
     float* log_w;

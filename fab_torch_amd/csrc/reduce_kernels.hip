@@ -26,7 +26,8 @@ __device__ __forceinline__ Msum msum_merge(const Msum& a, const Msum& b) {
     return Msum{m, a.s1 * ea + b.s1 * eb, a.s2 * ea * ea + b.s2 * eb * eb};
 }
 __device__ __forceinline__ Msum msum_push(const Msum& a, double x) {
-    if (x != x || a.m != a.m || x == INFINITY) return Msum{NAN, NAN, NAN};   // softmax(+inf) is NaN in torch
+    if (x != x || a.m != a.m) return Msum{NAN, NAN, NAN};
+    if (x == INFINITY) return Msum{x, NAN, NAN};        // softmax(+inf) is NaN in torch, logsumexp +inf: the maximum is kept
     if (x == -INFINITY) return a;                       // weight 0
     if (x <= a.m) {
         const double e = (double)expf((float)(x - a.m));   // fp32 exp (1e-7 rel), fp64 accumulation
@@ -35,6 +36,9 @@ __device__ __forceinline__ Msum msum_push(const Msum& a, double x) {
     const double r = (double)expf((float)(a.m - x));    // a.m == -inf -> 0
     return Msum{x, a.s1 * r + 1.0, a.s2 * r * r + 1.0};
 }
+
+// logsumexp of what was pushed: +inf where a weight was +inf and none NaN (torch.logsumexp; the sums are NaN there)
+__device__ __forceinline__ double msum_lse(const Msum& v) { return v.m == INFINITY ? v.m : v.m + log(v.s1); }
 
 // tree over the first `bdim` threads of the workgroup (every thread of the workgroup must call it: barriers)
 __device__ __forceinline__ Msum msum_block_reduce(Msum v, Msum* sh, int bdim) {
@@ -54,14 +58,15 @@ constexpr int ESS_MAX_BLOCKS = 1024;
 
 // chunk of values -> (max, sum exp(x - max), sum exp(2 (x - max))) with ONE rescale per chunk: the max is taken in fp32
 // first, the exponentials are fp32 (1e-7 relative) and summed in fp32 over the <= 16 values of the chunk, the running
-// totals are float64.  Same special values as torch's softmax: NaN or +inf anywhere -> NaN, -inf -> weight 0.
+// totals are float64.  Same special values as torch's softmax: NaN or +inf anywhere -> NaN sums, -inf -> weight 0.
 template <int NV>
 __device__ __forceinline__ Msum msum_push_chunk(const Msum& a, const float (&x)[NV]) {
     float m = -INFINITY;
-    bool bad = false;
+    bool nan = false, pinf = false;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) { bad |= (x[i] != x[i]) | (x[i] == INFINITY); m = fmaxf(m, x[i]); }
-    if (bad || a.m != a.m) return Msum{NAN, NAN, NAN};
+    for (int i = 0; i < NV; ++i) { nan |= x[i] != x[i]; pinf |= x[i] == INFINITY; m = fmaxf(m, x[i]); }
+    if (nan || a.m != a.m) return Msum{NAN, NAN, NAN};
+    if (pinf) return Msum{INFINITY, NAN, NAN};          // (as msum_push)
     if (m == -INFINITY) return a;                       // every weight of the chunk is zero
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -112,7 +117,7 @@ __device__ __forceinline__ void ess_final_body(const Msum* __restrict__ part, in
     v = msum_block_reduce(v, sh, bdim);
     if (threadIdx.x == 0) {
         const double ess = (v.s1 * v.s1 / v.s2) / (double)n;       // 1 / sum(softmax^2) / n
-        const double logz = v.m + log(v.s1) - log(n_norm);         // logsumexp - log(n_norm)
+        const double logz = msum_lse(v) - log(n_norm);             // logsumexp - log(n_norm)
         out[0] = (float)ess;
         out[1] = (float)logz;
         out[2] = (float)n;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_small(TailArgs a, int* __
         if (tid == 0) {
             const Msum v = msum_merge(msum_id(), part[0]);
             const double ess = (v.s1 * v.s1 / v.s2) / (double)n_out;
-            const double logz = v.m + log(v.s1) - log(a.n_norm);
+            const double logz = msum_lse(v) - log(a.n_norm);
             a.stats_out[0] = (float)ess; a.stats_out[1] = (float)logz; a.stats_out[2] = (float)n_out;
         }
     } else {

@@ -863,7 +863,12 @@ int fabhip_spline_ais_run(const fabhip_spline_ais_args* args, fabhip_stream_t st
 /* ------------------------------------------------------------------------------------------
  * ESS / log Z  (fab/utils/numerical.py:18-23, fab/sampling_methods/ais.py:80-86)
  * out[0] = normalised ESS of log_w[0..n), out[1] = logsumexp(log_w) - log(n_norm), out[2] = n used.
- * n is read from n_ptr (device) when n_ptr != NULL.
+ * n is read from n_ptr (device) when n_ptr != NULL; nothing at or beyond it is read.
+ * Special values as float64 torch gives them: a -inf weighs 0 and counts in n; a NaN makes ESS and
+ * log Z NaN; a +inf makes the ESS NaN (softmax) and log Z +inf (logsumexp); all -inf: ESS NaN, log Z -inf.
+ * n == 0 (the tail of a chain phase in which every row died - the reference raises there, ais.py:190-213,
+ * so this lies outside the oracle's domain): ESS NaN, log Z -inf, out[2] = 0; the compaction moves nothing
+ * and reports a count of 0.
  * ---------------------------------------------------------------------------------------- */
 size_t fabhip_ess_workspace_bytes(int64_t n);
 int fabhip_ess_logz(const float* log_w, int64_t n, const int32_t* n_ptr, double n_norm, float* out,
